@@ -6,7 +6,15 @@ catalog is split into two halves for 50 rounds, every host NotifyLeave()s the ot
 rounds (ExpireServer storm), the partition heals, and memberlist push-pull anti-entropy runs every
 10 rounds. All state is resident in HBM; the timed region is `gx_run_rounds(K)`.
 
-  python bench.py [--gpus N --steps K --warmup W] [--config cfg5|cfg2|cfg3|cfg4] [--no-converge]
+  python bench.py [--gpus N --steps K --warmup W] [--config cfg5|cfg2|cfg3|cfg4] [--dump-outputs DIR]
+  python bench.py --full [...] [--no-converge] [--no-cpu-baseline] [--no-lock-off] [--no-kernel-split]
+
+A plain run sets up, warms up, times the K steps and prints the result line: the headline figure and
+what the timed window's own counters say (the other fields are null). --full adds every measurement
+that takes runs of its own: the window without the ServicesState lock, the per-kernel split and
+rooflines, gossip-round spans, convergence runs, version spread and the CPU baseline.
+--dump-outputs DIR writes the state the timed steps left as DIR/<name>.npy (dump_outputs); the
+schedule is seeded, so two builds run with the same arguments can be compared array for array.
 
 Prints ONE JSON line (rank 0). N>1 runs one process per GPU (torch.distributed.run): the same
 cluster is sharded by host block over the N GPUs. Every round's cross-shard packets,
@@ -599,11 +607,72 @@ def cpu_baseline(cfg, warmup, steps, h_mt=16384, h_single=4096):
                               "sample": f"serial oracle at H={p1['n_hosts']}, {win} in {dt_1:.1f}s"}}
 
 
+DUMP_VIEWS = 4  # whole views written by --dump-outputs (H * S slots each; 25 MB at cfg 5)
+
+
+def dump_outputs(e, out_dir, seed):
+    """What a caller of the timed path holds after its last round, as <out_dir>/<name>.npy (float64,
+    status columns float32; 42 MB at cfg 5). Times are ns after t0 (exact in float64 where the packed
+    words are not).
+      view_rows          [DUMP_VIEWS] the views written whole: a sample of the hosts fixed by `seed`
+      view_updated_ns    [DUMP_VIEWS, R] each slot's Updated, 0 where the slot is empty
+      view_status        [DUMP_VIEWS, R] each slot's status (7 = empty)
+      minmax_updated_ns  [2, R] per record, the smallest and the largest slot word over ALL views
+      minmax_status      [2, R]   (gx_view_minmax: one wrong slot anywhere moves one of them)
+      host_state         [H, 16] gx_host_state of every host (queues, loopers, lock), fields in order
+      host_digests       [H, 2] gx_host_digests (FIFO jobs, sleepers, pending, lists), high and low half
+      stats              gx_stats after the last timed round, fields in order"""
+    import numpy as np
+    import torch
+    from sidecar_amd.abi import GxHostState, check
+    os.makedirs(out_dir, exist_ok=True)
+    H, R = e.H, e.H * e.S
+    rel = e.epoch - e.params.t0_ns
+
+    def unpack(words):
+        st = (words & np.uint64(7)).astype(np.float32)
+        t = (words >> np.uint64(3)).astype(np.int64) + rel
+        return np.where(st == 7, 0, t).astype(np.float64), st
+
+    def save(name, a):
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+    rows = np.sort(np.random.default_rng(seed).choice(H, size=min(DUMP_VIEWS, H), replace=False))
+    t, st = unpack(np.concatenate([e.read_views(int(v), int(v) + 1) for v in rows]))
+    save("view_rows", rows.astype(np.float64))
+    save("view_updated_ns", t)
+    save("view_status", st)
+    # gx_view_minmax writes engine memory: device memory for the HIP engine, host memory for the oracle
+    dev = torch.device(f"cuda:{e.params.device}" if e.backend.startswith("hip") else "cpu")
+    mn = torch.empty(R, dtype=torch.int64, device=dev)
+    mx = torch.empty(R, dtype=torch.int64, device=dev)
+    e.view_minmax(mn.data_ptr(), mx.data_ptr())
+    mm = torch.stack([mn, mx]).cpu().numpy().view(np.uint64) ^ np.uint64(1 << 63)  # the words themselves
+    t, st = unpack(mm)
+    save("minmax_updated_ns", t)
+    save("minmax_status", st)
+    hs = (GxHostState * H)()
+    check(e.lib.gx_read_hosts(e.h, 0, H, hs), "gx_read_hosts")
+    raw = np.frombuffer(hs, dtype=np.dtype(GxHostState))
+    cols = {n: raw[n].astype(np.float64) for n in raw.dtype.names}
+    cols["last_bcast_ns"] = (raw["last_bcast_ns"] + rel).astype(np.float64)  # epoch-relative, like slot times
+    save("host_state", np.stack([cols[n] for n in raw.dtype.names], axis=1))
+    dg = e.digests()
+    save("host_digests", np.stack([dg >> np.uint64(32), dg & np.uint64(0xFFFFFFFF)], axis=1).astype(np.float64))
+    save("stats", np.array([float(v) for v in e.stats().values()], dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline window, also run every other measurement (the window without the "
+                         "lock, the per-kernel split and rooflines, gossip spans, convergence runs, version "
+                         "spread, the CPU baseline); the --no-* options below pick among them")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the state the timed steps left (dump_outputs) as DIR/<name>.npy; one GPU only")
     ap.add_argument("--config", default="cfg5", choices=sorted(CONFIGS))
     ap.add_argument("--seed", type=int, default=0x5EED)
     ap.add_argument("--no-converge", action="store_true")
@@ -618,8 +687,11 @@ def main():
     # HBM bytes per launch of each kernel class over the window's own launches (profiles/r06/pmc_window.py)
     ap.add_argument("--pmc", default=os.path.join(ROOT, "profiles", "r06", "pmc_window.json"))
     args = ap.parse_args()
+    full = args.full
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    if args.dump_outputs and world > 1:
+        ap.error("--dump-outputs writes one engine's state: run it on one GPU")
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     import torch
@@ -658,6 +730,8 @@ def main():
     x1 = c.exchange_bytes()
     xfer = {k: x1[k] - x0[k] for k in x1} if x1 else None
     lock = lock_report(c.e.params, st0, st1, *((c.e.hosts(), c.round) if world == 1 else (None, None)))
+    if args.dump_outputs:
+        dump_outputs(c.e, args.dump_outputs, seed)
     c.close()
 
     split = {k: st1[k] - st0[k] for k in ("gossip_merges", "ae_merges", "local_merges")}
@@ -671,7 +745,7 @@ def main():
     # the same window without the ServicesState lock (lock_model = 0, the rounds-1..4 model): merges
     # proceed on hosts whose looper holds the lock; reported for comparison, never the headline
     lock_off = None
-    if world == 1 and not args.no_lock_off and c.e.params.lock_model:
+    if full and world == 1 and not args.no_lock_off and c.e.params.lock_model:
         c = Cluster(lib, args.config, seed, rank, world, local_rank, barrier, lock_model=0)
         if args.warmup:
             c.run_rounds(args.warmup)
@@ -712,7 +786,7 @@ def main():
         return out
 
     kern, kern_off = {}, None
-    if not args.no_kernel_split:
+    if full and not args.no_kernel_split:
         kern = kernel_split()
         if world == 1 and not args.no_lock_off and lock["lock_model"]:
             # the same window without the lock: every push-pull pair and every gossip receiver runs
@@ -771,9 +845,10 @@ def main():
                         lib, args.config, seed, local_rank, start=acc0, lock_model=0)
                 gossip["lock_off"] = lo
 
+    converge = full and not args.no_converge
     conv = None
     conv_lock_off = None
-    if not args.no_converge:
+    if converge:
         # a config may follow its converge run further, with a stored FIFO window that keeps it
         # lossless that long (CONFIGS[...]["converge"]; the window's size does not change any result
         # while no job is LOST, gx.h gx_job)
@@ -794,7 +869,7 @@ def main():
                              "note": "lock_model = 0 (not the reference: merges run on locked hosts)"}
     conv_ref = None
     ref = CONFIGS[args.config].get("ref_variant")
-    if ref and not args.no_converge:
+    if ref and converge:
         r, w, ran, _, qr, lr = run_converge(lib, ref, seed, rank, world, local_rank, barrier, args.converge_max,
                                             args.check_every)
         conv_ref = {"config": workload_text(ref), "rounds_to_converge": r,
@@ -804,7 +879,7 @@ def main():
     # per-version spread after the heal, or from round 0 where there is no partition (defined at any
     # cadence, on every line)
     heal = CONFIGS[args.config]["p"].get("partition_end", 0)
-    if world == 1 and not args.no_converge:
+    if world == 1 and converge:
         e = make_engine(lib, args.config, seed, local_rank)
         try:
             spread = version_spread(e, torch.device(f"cuda:{local_rank}"), heal, max(heal + 10, args.spread_max))
@@ -818,10 +893,10 @@ def main():
         finally:
             e.close()
     dis = None
-    if world == 1 and CONFIGS[args.config]["p"].get("churn_ppm") and not args.no_converge:
+    if world == 1 and CONFIGS[args.config]["p"].get("churn_ppm") and converge:
         dis = dissemination(lib, args.config, seed, local_rank)  # churn never converges: spread latency
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args.config, args.warmup, args.steps, h_mt=args.cpu_hosts)
 
     if rank == 0:

@@ -7,6 +7,6 @@ export TMPDIR=/tmp
 OUT=gpurun_out/prof_fd_$TAG
 mkdir -p $OUT
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/fd_depart -o run -- \
-  python3 bench.py --config fd_depart --steps 100 --no-converge --no-cpu-baseline > $OUT/fd_depart_bench.json
+  python3 bench.py --full --config fd_depart --steps 100 --no-converge --no-cpu-baseline > $OUT/fd_depart_bench.json
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/cfg5fd -o run -- \
-  python3 bench.py --config cfg5fd --steps 100 --no-converge --no-cpu-baseline > $OUT/cfg5fd_bench.json
+  python3 bench.py --full --config cfg5fd --steps 100 --no-converge --no-cpu-baseline > $OUT/cfg5fd_bench.json

@@ -36,3 +36,46 @@ def test_merges_by_source_and_time_share():
     assert bench.device_time_share({}) is None
     assert bench.expiry_report(dict(expired=3, false_expiries=2), dict(expired=10, false_expiries=8)) == \
         {"expired": 7, "false_expiries": 6}
+
+
+def test_dump_outputs_arrays(oracle_lib, tmp_path):
+    """--dump-outputs on the oracle (cfg1fd, 30 rounds): float arrays of the documented shapes that
+    restate the engine's own read-backs, identical from run to run."""
+    import numpy as np
+    from sidecar_amd.abi import GxHostState, GxStats
+    dumps, engines = [], []
+    for tag in ("a", "b"):
+        e = bench.make_engine(oracle_lib, "cfg1fd", 0x5EED, 0)
+        e.run_rounds(30)
+        engines.append(e)
+        bench.dump_outputs(e, str(tmp_path / tag), 0x5EED)
+        dumps.append({p.stem: np.load(p) for p in sorted((tmp_path / tag).glob("*.npy"))})
+    d = dumps[0]
+    H, R = e.H, e.H * e.S
+    assert {k: v.shape for k, v in d.items()} == {
+        "view_rows": (bench.DUMP_VIEWS,), "view_updated_ns": (bench.DUMP_VIEWS, R),
+        "view_status": (bench.DUMP_VIEWS, R), "minmax_updated_ns": (2, R), "minmax_status": (2, R),
+        "host_state": (H, len(GxHostState._fields_)), "host_digests": (H, 2),
+        "stats": (len(GxStats._fields_),)}
+    assert all(v.dtype in (np.float32, np.float64) for v in d.values())
+    for k in d:
+        assert np.array_equal(d[k], dumps[1][k]), k
+    # the sampled views are the engine's own words: status and Updated (ns after t0) of every slot
+    rows = d["view_rows"].astype(int)
+    assert len(set(rows)) == bench.DUMP_VIEWS and rows.min() >= 0 and rows.max() < H
+    for i, v in enumerate(rows):
+        ts, st = e.read_view(int(v))
+        assert np.array_equal(d["view_status"][i], st.astype(np.float32))
+        live = st != 7
+        assert np.array_equal(d["view_updated_ns"][i][live], (ts[live] - e.params.t0_ns).astype(np.float64))
+        # every view's word lies between the per-record min and max over all views
+        held = live & (d["minmax_status"][0] != 7)  # an empty slot is the smallest word
+        assert (d["minmax_updated_ns"][0][held] <= d["view_updated_ns"][i][held]).all()
+        assert (d["view_updated_ns"][i][live] <= d["minmax_updated_ns"][1][live]).all()
+    st = e.stats()
+    assert d["stats"].tolist() == [float(v) for v in st.values()]
+    assert d["stats"][list(st).index("fd_probes")] == st["fd_probes"] > 0
+    dg = e.digests()
+    assert np.array_equal(d["host_digests"][:, 0] * 2.0 ** 32 + d["host_digests"][:, 1], dg.astype(np.float64))
+    for e in engines:
+        e.close()
