@@ -31,6 +31,7 @@
 #include <algorithm>
 #include <deque>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 
@@ -174,6 +175,11 @@ static int ensure_api(gx_engine *e, size_t bytes) {
 }
 
 static bool own(const gx_engine *e, uint32_t v) { return v >= e->d.lo && v < e->d.lo + e->d.Hl; }
+// The two runtime flags that kernel variants are built for, each read here only:
+// VEC, an even row length (view rows stream as 16-B pairs of slots)
+static bool vec_of(const gx_engine *e) { return e->d.R % 2 == 0; }
+// EV, some view has a listener (the ChangeEvent variants)
+static bool ev_of(const gx_engine *e) { return !e->log_views.empty(); }
 // push-pull also merges memberlist state (mergeState)
 static bool pp_state(const Dev &d) { return d.p.fd_enable && d.p.fd_push_pull_state; }
 static int64_t now_of(const gx_engine *e) { return e->d.p.t0_ns + e->d.round * e->d.p.round_ns; }
@@ -295,13 +301,20 @@ static int sync_check(gx_engine *e) {
   HIPCHK(hipGetLastError());
   int rc = take_device_error(e);
   if (rc) return rc;
-  return e->log_views.empty() ? GX_OK : deliver_events(e);
+  return ev_of(e) ? deliver_events(e) : GX_OK;
+}
+
+// One scalar result of an ABI call's kernel: copied back on the engine's stream, then sync_check.
+template <class T>
+static int read_back(gx_engine *e, const void *dev, T *host) {
+  HIPCHK(hipMemcpyAsync(host, dev, sizeof(T), hipMemcpyDeviceToHost, e->stream));
+  return sync_check(e);
 }
 
 // End of a sharded phase call: with async phases (and no listeners to feed) the caller's stream
 // orders the next step, so only launch errors are checked here.
 static int phase_done(gx_engine *e) {
-  if (e->async_phases && e->log_views.empty()) {
+  if (e->async_phases && !ev_of(e)) {
     HIPCHK(hipGetLastError());
     return GX_OK;
   }
@@ -310,7 +323,35 @@ static int phase_done(gx_engine *e) {
 
 static inline unsigned nblk(size_t n, unsigned t) { return (unsigned)((n + t - 1) / t); }
 
-// Phases 0-3 (wake, owners, expiry scan, storm, GetBroadcasts) for this engine's hosts.
+// Runtime flags -> template arguments: f is a generic lambda that gets one std::integral_constant
+// per flag and names its kernel with them, k_scan<V(), E()><<<...>>>(...). Every combination is
+// instantiated, so these serve only where all of them are built anyway; a subset stays an if.
+template <class F>
+static void with_flag(bool a, F &&f) {
+  if (a) f(std::true_type{});
+  else f(std::false_type{});
+}
+template <class F>
+static void with_flags(bool a, bool b, F &&f) {
+  with_flag(a, [&](auto A) { with_flag(b, [&](auto B) { f(A, B); }); });
+}
+// k_send's OWN: services per lane of the 4-lane owner teams, 0 = the owner ticks are not in k_send
+static int own_class(uint32_t S) { return S <= 4 ? 1 : S <= 8 ? 2 : 4; }
+template <class F>
+static void with_own(int own, F &&f) {
+  if (own == 0) f(std::integral_constant<int, 0>{});
+  else if (own == 1) f(std::integral_constant<int, 1>{});
+  else if (own == 2) f(std::integral_constant<int, 2>{});
+  else f(std::integral_constant<int, 4>{});
+}
+
+// d.in_round for the launches of a round phase: ExpireServer waits for a held lock (gx.h lock_model)
+struct InRound {
+  Dev &d;
+  explicit InRound(Dev &d_) : d(d_) { d.in_round = 1; }
+  ~InRound() { d.in_round = 0; }
+};
+
 // k_owner with a team of T >= S lanes per host (lane s = service s)
 template <int T>
 static void launch_owner(const Dev &d, hipStream_t s) {
@@ -355,15 +396,38 @@ static int scan_probe_end(gx_engine *e) {
   return GX_OK;
 }
 
+// k_send's variant. X: departures or the detector; SCAN: the round's expiry scans run in k_send's
+// prologue; own: own_class(S) when the owner ticks run there too, else 0; PLAN: send_planned.
+struct SendSel {
+  bool x, scan, plan;
+  int own;
+};
+// The whole table of k_send variants: (X, PLAN) without both at once; with SCAN, VEC x EV x OWN; without
+// it one variant each (k_send's static_asserts state the same).
+// 4 lanes per host: measured best of 1/4/8/16/64 (profiles/send_team.sh);
+// teams of 2 / 8 lanes measured 25.6 / 28.7 vs 21.1 us (profiles/r02/gossip/send_team_ab.log)
+static void launch_send(gx_engine *e, SendSel sel, int do_bt) {
+  const Dev &d = e->d;
+  const unsigned g = nblk(d.Hl, 64);
+  hipStream_t s = e->stream;
+  auto rest = [&](auto X, auto P) {
+    if (!sel.scan) {
+      k_send<4, X(), false, false, false, 0, P()><<<g, 256, 0, s>>>(d, do_bt);
+      return;
+    }
+    with_flags(vec_of(e), ev_of(e), [&](auto V, auto E) {
+      with_own(sel.own, [&](auto O) { k_send<4, X(), true, V(), E(), O(), P()><<<g, 256, 0, s>>>(d, do_bt); });
+    });
+  };
+  if (sel.plan) rest(std::false_type{}, std::true_type{});
+  else with_flag(sel.x, [&](auto X) { rest(X, std::false_type{}); });
+}
+
 // Phases 0-3 (wake, owners, expiry scan, storm, GetBroadcasts) for this engine's hosts.
 static int round_send_impl(gx_engine *e) {
   Dev &d = e->d;
   set_round_fields(e);
-  d.in_round = 1;  // ExpireServer waits for a held lock (gx.h lock_model); reset after the launches
-  struct InRound {
-    Dev &d;
-    ~InRound() { d.in_round = 0; }
-  } in_round_guard{d};
+  InRound in_round_guard(d);
   {
     int rc = scan_probe_begin(e);
     if (rc) return rc;
@@ -377,69 +441,34 @@ static int round_send_impl(gx_engine *e) {
     k_wake<<<nblk(d.Hl, 64), 64, 0, s>>>(d);
     k_probe<4><<<nblk(d.Hl, 64), 256, 0, s>>>(d);
   }
-  bool vec = (d.R % 2) == 0;
+  const bool vec = vec_of(e), ev = ev_of(e);
   const bool storm = d.p.storm_round >= 0 && d.round == d.p.storm_round && d.H >= 2;
   // BroadcastTombstones' SendServices is queued before the detector's and the storm's jobs
   const bool bt_apart = d.p.fd_enable || storm;
+  // with the tick finished in k_send, the expiry scans run in k_send's prologue (no k_scan launch)
+  const bool scan_in_send = !bt_apart && d.K && !e->scan_heavy;
   // a round without the detector or the storm: owner ticks, expiry scans and sends in one launch
   // (S <= 16: owner teams of the send's 4 lanes with up to 4 services each)
-  const bool fused = !bt_apart && d.K && d.S <= 16 && !e->scan_heavy;
+  const bool fused = scan_in_send && d.S <= 16;
   // planned GetBroadcasts (send_planned): record budget, no detector or departures, re-armed
   // passes sleep; teams of 4 lanes per host
   const bool plan = !d.p.limit_bytes && d.p.retransmit_rounds > 0 && !d.departures && !d.p.fd_enable;
-  if (fused && plan) {
-    LaunchTimer t(e, GX_K_SEND);
-    const unsigned g = nblk(d.Hl, 64);
-    const bool ev = !e->log_views.empty();
-#define GX_TSP(SPL)                                                                                               \
-  (vec ? (ev ? k_send<4, false, true, true, true, SPL, true> : k_send<4, false, true, true, false, SPL, true>)    \
-       : (ev ? k_send<4, false, true, false, true, SPL, true> : k_send<4, false, true, false, false, SPL, true>)) \
-      <<<g, 256, 0, s>>>(d, 1)
-    if (d.S <= 4) GX_TSP(1);
-    else if (d.S <= 8) GX_TSP(2);
-    else GX_TSP(4);
-#undef GX_TSP
-    HIPCHK(hipGetLastError());
-    return scan_probe_end(e);
-  }
-  if (fused) {
-    LaunchTimer t(e, GX_K_SEND);
-    const unsigned g = nblk(d.Hl, 64);
-    const bool ev = !e->log_views.empty();
-#define GX_TS(X, SPL)                                                                                    \
-  (vec ? (ev ? k_send<4, X, true, true, true, SPL> : k_send<4, X, true, true, false, SPL>)             \
-       : (ev ? k_send<4, X, true, false, true, SPL> : k_send<4, X, true, false, false, SPL>))<<<g, 256, 0, s>>>(d, 1)
-#define GX_TICK_SEND(SPL) \
-  if (d.departures) GX_TS(true, SPL); else GX_TS(false, SPL)
-    if (d.S <= 4) {
-      GX_TICK_SEND(1);
-    } else if (d.S <= 8) {
-      GX_TICK_SEND(2);
-    } else {
-      GX_TICK_SEND(4);
-    }
-#undef GX_TICK_SEND
-#undef GX_TS
-    HIPCHK(hipGetLastError());
-    return scan_probe_end(e);
-  }
-  {
+  const SendSel sel{d.p.fd_enable || d.departures, scan_in_send, plan, fused ? own_class(d.S) : 0};
+  if (!fused) {
     LaunchTimer t(e, GX_K_OWNER);
     owner_launch(d, s);
   }
-  // with the tick finished in k_send, the expiry scans run in k_send's prologue (no k_scan launch)
-  const bool scan_in_send = !bt_apart && d.K && !e->scan_heavy;
   if (!scan_in_send) {
     LaunchTimer t(e, GX_K_SCAN);
-    const bool ev = !e->log_views.empty();
     const unsigned grid = d.Hl < SCAN_GRID ? d.Hl : SCAN_GRID;
     if (vec && !ev && e->scan_nch > 1) {  // rows split over blocks, then joined per view
       k_scan_split<true><<<SCAN_GRID, 256, GX_SCAN_WAVE ? 4 * sizeof(grec) * d.L : 0, s>>>(d, e->scan_tmp, e->scan_chunk,
                                                                                          e->scan_nch);
       k_scan_join<<<grid, 256, 0, s>>>(d, e->scan_tmp, e->scan_chunk, e->scan_nch);
     } else {
-      (vec ? (ev ? k_scan<true, true> : k_scan<true, false>) : (ev ? k_scan<false, true> : k_scan<false, false>))
-          <<<grid, 256, 0, s>>>(d, d.scan_list, d.L, d.L, d.scan_cnt, -1);
+      with_flags(vec, ev, [&](auto V, auto E) {
+        k_scan<V(), E()><<<grid, 256, 0, s>>>(d, d.scan_list, d.L, d.L, d.scan_cnt, -1);
+      });
     }
     if (bt_apart) k_bt_finish<<<nblk(d.Hl, 256), 256, 0, s>>>(d);
   }
@@ -449,38 +478,16 @@ static int round_send_impl(gx_engine *e) {
   }
   if (storm) {
     LaunchTimer t(e, GX_K_STORM);
-    const bool ev = !e->log_views.empty();
     // nontemporal row stream: 30.3 -> 27.9 ms at cfg 5 (profiles/ab/storm_nt_ab_r02.log)
-    if (d.S >= 2 && 64 % d.S == 0)
-      (ev ? k_storm_p2<true, true> : k_storm_p2<false, true>)<<<d.Hl, 256, 0, s>>>(d);
-    else (ev ? k_storm<true> : k_storm<false>)<<<d.Hl, 256, 0, s>>>(d);
+    with_flag(ev, [&](auto E) {
+      if (d.S >= 2 && 64 % d.S == 0) k_storm_p2<E(), true><<<d.Hl, 256, 0, s>>>(d);
+      else k_storm<E()><<<d.Hl, 256, 0, s>>>(d);
+    });
   }
   {
     LaunchTimer t(e, GX_K_SEND);
     if (d.p.fd_enable) k_fd_send<<<nblk(d.Hl, 64), 64, 0, s>>>(d);  // memberlist's targets + messages
-    // 4 lanes per host: measured best of 1/4/8/16/64 (profiles/send_team.sh)
-    const bool ev = !e->log_views.empty();
-    const unsigned g = nblk(d.Hl, 64);
-    // teams of 2 / 8 lanes measured 25.6 / 28.7 vs 21.1 us (profiles/r02/gossip/send_team_ab.log)
-    if (plan) {
-      if (scan_in_send)
-        (vec ? (ev ? k_send<4, false, true, true, true, 0, true> : k_send<4, false, true, true, false, 0, true>)
-             : (ev ? k_send<4, false, true, false, true, 0, true> : k_send<4, false, true, false, false, 0, true>))
-            <<<g, 256, 0, s>>>(d, 1);
-      else
-        k_send<4, false, false, false, false, 0, true><<<g, 256, 0, s>>>(d, bt_apart ? 0 : 1);
-    } else if (scan_in_send) {
-      if (d.departures)
-        (vec ? (ev ? k_send<4, true, true, true, true> : k_send<4, true, true, true, false>)
-             : (ev ? k_send<4, true, true, false, true> : k_send<4, true, true, false, false>))<<<g, 256, 0, s>>>(d, 1);
-      else
-        (vec ? (ev ? k_send<4, false, true, true, true> : k_send<4, false, true, true, false>)
-             : (ev ? k_send<4, false, true, false, true> : k_send<4, false, true, false, false>))<<<g, 256, 0, s>>>(d, 1);
-    } else if (d.p.fd_enable || d.departures) {
-      k_send<4, true><<<g, 256, 0, s>>>(d, bt_apart ? 0 : 1);
-    } else {
-      k_send<4, false><<<g, 256, 0, s>>>(d, bt_apart ? 0 : 1);
-    }
+    launch_send(e, sel, bt_apart ? 0 : 1);
   }
   HIPCHK(hipGetLastError());
   return scan_probe_end(e);
@@ -501,25 +508,29 @@ static int round_send_impl(gx_engine *e) {
 #define GX_MERGE_SMALL_HL 16384  // 16 receivers per block below this many local hosts: merge 2.0 -> 1.1 ms (cfg 2)
                                  // and 2.4 -> 1.5 ms (cfg 4) over 60 rounds lock off (profiles/r05/ab/merge_nr16_*)
 #endif
+// k_merge_seg over every receiver: 16 receivers per block at MERGE_WPE_GM waves per SIMD (`small`) or
+// the default 64; 32-bit sort keys while R < 2^26 (K32).
+static void launch_merge(gx_engine *e, bool small) {
+  const Dev &d = e->d;
+  const unsigned g = nblk(d.Hl, small ? 16u : (unsigned)MERGE_NR);
+  with_flags(d.R < (1u << 26), ev_of(e), [&](auto K32, auto E) {
+    if (small) k_merge_seg<K32(), E(), 16, MERGE_WPE_GM><<<g, 64 * MERGE_WAVES, 0, e->stream>>>(d);
+    else k_merge_seg<K32(), E()><<<g, 64 * MERGE_WAVES, 0, e->stream>>>(d);
+  });
+}
+
 // Phase 4: gather-then-merge of every receiver's inbox (local and received packets).
 static int round_merge_impl(gx_engine *e) {
   Dev &d = e->d;
   set_round_fields(e);
-  d.in_round = 1;
-  struct InRound {
-    Dev &d;
-    ~InRound() { d.in_round = 0; }
-  } in_round_guard{d};
+  InRound in_round_guard(d);
   hipStream_t s = e->stream;
   if (d.p.lock_readers) {  // waiting push-pull merges of hosts unlocked now, before their pipelines
     LaunchTimer t(e, GX_K_AE);
-    const bool vec = (d.R % 2) == 0, ev = !e->log_views.empty();
-    (vec ? (ev ? k_defer_drain<true, true> : k_defer_drain<true, false>)
-         : (ev ? k_defer_drain<false, true> : k_defer_drain<false, false>))<<<d.P, 256, 0, s>>>(d);
+    with_flags(vec_of(e), ev_of(e), [&](auto V, auto E) { k_defer_drain<V(), E()><<<d.P, 256, 0, s>>>(d); });
   }
   if (d.K) {
     LaunchTimer t(e, GX_K_MERGE);
-    const bool ev = !e->log_views.empty();
     // receivers routed by their live records. GossipMessages > 1: inboxes of hundreds of live
     // records, each folded by a whole wave tile by tile, so more waves in flight (16 receivers per
     // block, 4 waves per SIMD: 10% faster than 3 in the GM 15 accepting stretch,
@@ -539,15 +550,7 @@ static int round_merge_impl(gx_engine *e) {
     const bool lapp = GX_LOCK_APPEND && d.p.lock_model && !d.p.fd_handoff_shared && d.NG == 1 && d.Hl >= GX_LOCK_APPEND_HL;
     if (lapp) k_lock_append<<<nblk(d.Hl, 16), 256, 0, s>>>(d);
     const bool small = d.NG > 1 || d.Hl < GX_MERGE_SMALL_HL || (d.p.lock_model && !(GX_MERGE_LAPP_NR64 && lapp));
-    const unsigned g = nblk(d.Hl, small ? 16u : (unsigned)MERGE_NR);
-    if (small) {
-      if (d.R < (1u << 26)) (ev ? k_merge_seg<true, true, 16, MERGE_WPE_GM> : k_merge_seg<true, false, 16, MERGE_WPE_GM>)<<<g, 64 * MERGE_WAVES, 0, s>>>(d);
-      else (ev ? k_merge_seg<false, true, 16, MERGE_WPE_GM> : k_merge_seg<false, false, 16, MERGE_WPE_GM>)<<<g, 64 * MERGE_WAVES, 0, s>>>(d);
-    } else if (d.R < (1u << 26)) {
-      (ev ? k_merge_seg<true, true> : k_merge_seg<true, false>)<<<g, 64 * MERGE_WAVES, 0, s>>>(d);
-    } else {
-      (ev ? k_merge_seg<false, true> : k_merge_seg<false, false>)<<<g, 64 * MERGE_WAVES, 0, s>>>(d);
-    }
+    launch_merge(e, small);
   }
   if (d.p.fd_enable && d.K) {  // the packets' memberlist messages, after the catalog merge
     LaunchTimer t(e, GX_K_FD);
@@ -600,9 +603,17 @@ static bool ae_partner(const Dev &d, uint32_t i, uint32_t *out) {
 // gx.h lock_readers: the read-locked exchanges of the last push-pull launch (k_ae_ro)
 static void ae_ro_launch(gx_engine *e, const uint32_t *pa, const uint32_t *pb, uint64_t key0, uint64_t key1, uint32_t np) {
   const Dev &d = e->d;
-  const bool vec = (d.R % 2) == 0, ev = !e->log_views.empty();
-  (vec ? (ev ? k_ae_ro<true, true> : k_ae_ro<true, false>) : (ev ? k_ae_ro<false, true> : k_ae_ro<false, false>))<<<1, 256, 0, e->stream>>>(
-      d, pa, pb, key0, key1, np);
+  with_flags(vec_of(e), ev_of(e),
+             [&](auto V, auto E) { k_ae_ro<V(), E()><<<1, 256, 0, e->stream>>>(d, pa, pb, key0, key1, np); });
+}
+// The planned pairs' exchange: the ChangeEvent variant while some view has a listener, else two
+// tiles in flight where the caller asks (pf2), else one.
+static void launch_ae_plan(gx_engine *e, bool pf2, unsigned np, hipStream_t st, const uint32_t *pa, const uint32_t *pb,
+                           const int32_t *prow, const uint8_t *pcount, const AeIn &in, const uint8_t *skip) {
+  const bool ev = ev_of(e);
+  with_flag(vec_of(e), [&](auto V) {
+    (ev ? k_ae_plan_ev<V()> : pf2 ? k_ae_plan_pf2<V()> : k_ae_plan<V()>)<<<np, 256, 0, st>>>(e->d, pa, pb, prow, pcount, in, skip);
+  });
 }
 static int ae_initiate(gx_engine *e) {
   Dev &d = e->d;
@@ -634,15 +645,13 @@ static int ae_initiate(gx_engine *e) {
     e->pp_host[n + at] = ib[t];
   }
   HIPCHK(hipMemcpyAsync(e->pp_dev, e->pp_host.data(), sizeof(uint32_t) * 2 * n, hipMemcpyHostToDevice, e->stream));
-  const bool vec = (d.R % 2) == 0, ev = !e->log_views.empty();
   AeIn none;
   memset(&none, 0, sizeof(none));
   LaunchTimer t(e, GX_K_AE);
   for (uint32_t q = 0; q < nb; q++) {
     const uint32_t *pa = e->pp_dev + off[q], *pb = e->pp_dev + n + off[q];
     const unsigned np = off[q + 1] - off[q];
-    if (ev) (vec ? k_ae_plan_ev<true> : k_ae_plan_ev<false>)<<<np, 256, 0, e->stream>>>(d, pa, pb, e->pp_prow, nullptr, none, nullptr);
-    else (vec ? k_ae_plan<true> : k_ae_plan<false>)<<<np, 256, 0, e->stream>>>(d, pa, pb, e->pp_prow, nullptr, none, nullptr);
+    launch_ae_plan(e, false, np, e->stream, pa, pb, e->pp_prow, nullptr, none, nullptr);
     if (d.p.lock_readers) ae_ro_launch(e, pa, pb, 0, 0, np);  // the batch's read-locked exchanges
   }
   return GX_OK;
@@ -653,7 +662,6 @@ static int ae_whole_impl(gx_engine *e) {
   Dev &d = e->d;
   set_round_fields(e);
   hipStream_t s = e->stream;
-  bool vec = (d.R % 2) == 0;
   if (ae_round(e) && d.p.push_pull_mode == GX_PP_INITIATE) {
     int rc = ae_initiate(e);
     if (rc) return rc;
@@ -673,7 +681,7 @@ static int ae_whole_impl(gx_engine *e) {
       LaunchTimer t(e, GX_K_AE);
       // PF = 1: deeper prefetch measured within noise (profiles/ae_variants.sh)
       // the ChangeEvent variant only while some view has a listener
-      const bool ev = !e->log_views.empty();
+      const bool vec = vec_of(e), ev = ev_of(e);
       // nontemporal row loads and stores: -1% over the bench window (profiles/ab/ae_nt_ab_r02.log)
       // under the lock model chunks of pairs per block (ae_round_pairs): a round whose pairs a lock
       // skips costs one round trip per chunk, not a block per pair
@@ -1237,6 +1245,11 @@ static int stage_recs(gx_engine *e, const gx_service *svcs, uint32_t n, size_t o
   return GX_OK;
 }
 
+// TombstoneOthersServices over one view for an ABI call: one block, always the ChangeEvent variant.
+static void scan_one_view(gx_engine *e, uint32_t view, grec *list, uint32_t cap, uint32_t *cnt) {
+  with_flag(vec_of(e), [&](auto V) { k_scan<V(), true><<<1, 256, 0, e->stream>>>(e->d, list, 0, cap, cnt, (int)view); });
+}
+
 static int api_add(gx_engine *e, const uint32_t *views, uint32_t fixed_view, const gx_service *svcs, uint32_t n,
                    int src, uint32_t *n_acc) {
   HIPCHK(hipSetDevice(e->device));
@@ -1253,11 +1266,9 @@ static int api_add(gx_engine *e, const uint32_t *views, uint32_t fixed_view, con
   set_round_fields(e);
   k_api_add<<<1, 64, 0, e->stream>>>(e->d, views ? dviews : nullptr, fixed_view, drec, n, src, dacc);
   uint32_t acc = 0;
-  HIPCHK(hipMemcpyAsync(&acc, dacc, sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
-  rc = sync_check(e);
-  if (rc) return rc;
-  if (n_acc) *n_acc = acc;
-  return GX_OK;
+  rc = read_back(e, dacc, &acc);
+  if (!rc && n_acc) *n_acc = acc;
+  return rc;
 }
 
 int gx_add_service_entries(gx_engine *e, const uint32_t *views, const gx_service *svcs, uint32_t n,
@@ -1280,11 +1291,8 @@ int gx_merge(gx_engine *e, uint32_t dst, uint32_t src) {
   if (!e || !own(e, dst) || !own(e, src)) return GX_EINVAL;
   HIPCHK(hipSetDevice(e->device));
   set_round_fields(e);
-  const bool ev = !e->log_views.empty();
-  if (e->d.R % 2 == 0 && !ev) k_merge_views<true, false><<<1, 256, 0, e->stream>>>(e->d, dst, src);
-  else if (e->d.R % 2 == 0) k_merge_views<true, true><<<1, 256, 0, e->stream>>>(e->d, dst, src);
-  else if (!ev) k_merge_views<false, false><<<1, 256, 0, e->stream>>>(e->d, dst, src);
-  else k_merge_views<false, true><<<1, 256, 0, e->stream>>>(e->d, dst, src);
+  with_flags(vec_of(e), ev_of(e),
+             [&](auto V, auto E) { k_merge_views<V(), E()><<<1, 256, 0, e->stream>>>(e->d, dst, src); });
   return sync_check(e);
 }
 
@@ -1296,11 +1304,9 @@ int gx_tombstone_others(gx_engine *e, uint32_t view, gx_service *out, uint32_t c
   uint32_t *dcnt = (uint32_t *)e->api_dev;
   grec *dlist = (grec *)((char *)e->api_dev + 256);
   set_round_fields(e);
-  (e->d.R % 2 == 0 ? k_scan<true, true> : k_scan<false, true>)<<<1, 256, 0, e->stream>>>(e->d, dlist, 0, cap, dcnt,
-                                                                                        (int)view);
+  scan_one_view(e, view, dlist, cap, dcnt);
   uint32_t n = 0;
-  HIPCHK(hipMemcpyAsync(&n, dcnt, sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
-  rc = sync_check(e);
+  rc = read_back(e, dcnt, &n);
   if (rc) return rc;
   uint32_t m = n < cap ? n : cap;
   if (m) {
@@ -1326,8 +1332,7 @@ int gx_tombstone_services(gx_engine *e, uint32_t host, const uint16_t *running, 
   set_round_fields(e);
   k_api_tomb<<<1, 64, 0, e->stream>>>(e->d, host, mask, (uint64_t *)e->api_dev);
   uint64_t m = 0;
-  HIPCHK(hipMemcpyAsync(&m, e->api_dev, sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream));
-  rc = sync_check(e);
+  rc = read_back(e, e->api_dev, &m);
   if (rc) return rc;
   uint32_t n = 0;
   int64_t now = now_of(e);
@@ -1354,11 +1359,9 @@ int gx_expire_server(gx_engine *e, uint32_t view, uint32_t owner, int *expired) 
   set_round_fields(e);
   k_api_expire<<<1, 64, 0, e->stream>>>(e->d, view, owner, (uint32_t *)e->api_dev);
   uint32_t x = 0;
-  HIPCHK(hipMemcpyAsync(&x, e->api_dev, sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
-  rc = sync_check(e);
-  if (rc) return rc;
-  if (expired) *expired = (int)x;
-  return GX_OK;
+  rc = read_back(e, e->api_dev, &x);
+  if (!rc && expired) *expired = (int)x;
+  return rc;
 }
 
 int gx_notify_leave(gx_engine *e, uint32_t view, uint32_t node) { return gx_expire_server(e, view, node, nullptr); }
@@ -1400,8 +1403,7 @@ int gx_broadcast_tombstones(gx_engine *e, uint32_t host, const gx_service *list,
   uint32_t *dcnt = (uint32_t *)e->api_dev;
   grec *dlist = (grec *)((char *)e->api_dev + 256);
   set_round_fields(e);
-  (e->d.R % 2 == 0 ? k_scan<true, true> : k_scan<false, true>)<<<1, 256, 0, e->stream>>>(e->d, dlist, 0, e->d.L, dcnt,
-                                                                                        (int)host);
+  scan_one_view(e, host, dlist, e->d.L, dcnt);
   k_api_bt<<<1, 64, 0, e->stream>>>(e->d, host, mask, dlist, dcnt);
   return sync_check(e);
 }
@@ -1425,11 +1427,9 @@ int gx_is_new_service(gx_engine *e, uint32_t view, const gx_service *svc, int *o
   if (rc) return rc;
   k_api_is_new<<<1, 64, 0, e->stream>>>(e->d, view, g.w, g.r, (uint32_t *)e->api_dev);
   uint32_t x = 0;
-  HIPCHK(hipMemcpyAsync(&x, e->api_dev, sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
-  rc = sync_check(e);
-  if (rc) return rc;
-  *out = (int)x;
-  return GX_OK;
+  rc = read_back(e, e->api_dev, &x);
+  if (!rc) *out = (int)x;
+  return rc;
 }
 
 static int getb_impl(gx_engine *e, uint32_t host, uint32_t limit, uint32_t limit_bytes, uint32_t overhead,
@@ -1442,8 +1442,7 @@ static int getb_impl(gx_engine *e, uint32_t host, uint32_t limit, uint32_t limit
   set_round_fields(e);
   k_api_getb<<<1, 64, 0, e->stream>>>(e->d, host, limit, dpk, dn, limit_bytes, overhead);
   uint32_t n = 0;
-  HIPCHK(hipMemcpyAsync(&n, dn, sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
-  rc = sync_check(e);
+  rc = read_back(e, dn, &n);
   if (rc) return rc;
   if (n) {
     std::vector<grec> tmp(n);
@@ -1912,6 +1911,9 @@ static size_t slot_bytes(const Dev &d) {
   return 16 + 16ull * d.p.packet_cap + (d.p.fd_enable ? 16ull * d.p.fd_msg_cap : 0);
 }
 static size_t dig_bytes(const gx_engine *e) { return dig_stride(e->d, e->nblk); }
+// the sharded push-pull's lead and return kernels with the offsets up front, a wave per block
+// (profiles/ab_shard_ae.sh), while a row's digest blocks fit their LDS tables
+static bool ae_wave_blocks(const gx_engine *e) { return e->nblk <= XS_MAXB; }
 
 int gx_round_send(gx_engine *e) {
   if (!e) return GX_EINVAL;
@@ -1920,16 +1922,10 @@ int gx_round_send(gx_engine *e) {
   return rc ? rc : phase_done(e);
 }
 
-// Entries of this shard's packets bound for other shards, grouped by destination shard in key
-// order; sizes in bytes per shard.
-int gx_outbox_bytes(gx_engine *e, uint64_t *bytes) {
-  if (!e || !bytes) return GX_EINVAL;
-  HIPCHK(hipSetDevice(e->device));
-  Dev &d = e->d;
-  for (uint32_t g = 0; g < d.G; g++) bytes[g] = 0;
-  e->n_ob = 0;
-  e->ob_async = false;
-  if (d.G < 2 || !d.K) return GX_OK;
+// This round's outbox plan: the entries of this shard's packets bound for other shards, grouped by
+// destination shard in key order (ob_entries), and the packets per destination (ob_counts[0..G)).
+static void outbox_plan(gx_engine *e) {
+  const Dev &d = e->d;
   set_round_fields(e);
   const size_t ne = (size_t)d.Hl * d.KE;
   const uint32_t nchunk = (uint32_t)((ne + 255) / 256);
@@ -1938,6 +1934,18 @@ int gx_outbox_bytes(gx_engine *e, uint64_t *bytes) {
   k_ob_count<<<nchunk, 256, lds, e->stream>>>(d, ccnt);
   k_ob_scan<<<1, 256, 0, e->stream>>>(d, ccnt, nchunk, off, e->ob_counts);
   k_ob_fill<<<nchunk, 256, lds, e->stream>>>(d, off, e->ob_entries);
+}
+
+// The outbox plan, read back: sizes in bytes per shard.
+int gx_outbox_bytes(gx_engine *e, uint64_t *bytes) {
+  if (!e || !bytes) return GX_EINVAL;
+  HIPCHK(hipSetDevice(e->device));
+  Dev &d = e->d;
+  for (uint32_t g = 0; g < d.G; g++) bytes[g] = 0;
+  e->n_ob = 0;
+  e->ob_async = false;
+  if (d.G < 2 || !d.K) return GX_OK;
+  outbox_plan(e);
   std::vector<uint32_t> cnt(d.G);
   HIPCHK(hipMemcpyAsync(cnt.data(), e->ob_counts, sizeof(uint32_t) * d.G, hipMemcpyDeviceToHost, e->stream));
   int rc = sync_check(e);
@@ -1961,14 +1969,7 @@ int gx_outbox_sizes_async(gx_engine *e, uint64_t *bytes) {
     HIPCHK(hipMemsetAsync(bytes, 0, sizeof(uint64_t) * d.G, e->stream));
     return phase_done(e);
   }
-  set_round_fields(e);
-  const size_t ne = (size_t)d.Hl * d.KE;
-  const uint32_t nchunk = (uint32_t)((ne + 255) / 256);
-  uint32_t *ccnt = e->ob_counts + d.G, *off = ccnt + (size_t)nchunk * d.G;
-  const size_t lds = sizeof(uint32_t) * 4 * d.G;
-  k_ob_count<<<nchunk, 256, lds, e->stream>>>(d, ccnt);
-  k_ob_scan<<<1, 256, 0, e->stream>>>(d, ccnt, nchunk, off, e->ob_counts);
-  k_ob_fill<<<nchunk, 256, lds, e->stream>>>(d, off, e->ob_entries);
+  outbox_plan(e);
   k_ob_bytes<<<1, 64, 0, e->stream>>>(d, e->ob_counts, (unsigned long long *)bytes, e->ob_total);
   e->ob_async = true;
   return phase_done(e);
@@ -2078,14 +2079,7 @@ int gx_outbox_pack_planned(gx_engine *e, void *buf, uint64_t cap) {
   for (uint32_t g = 0; g < d.G; g++) slots += e->xbound.n[g];
   if (cap < slots * slot_bytes(d)) return GX_EINVAL;
   HIPCHK(hipSetDevice(e->device));
-  set_round_fields(e);
-  const size_t ne = (size_t)d.Hl * d.KE;
-  const uint32_t nchunk = (uint32_t)((ne + 255) / 256);
-  uint32_t *ccnt = e->ob_counts + d.G, *off = ccnt + (size_t)nchunk * d.G;
-  const size_t lds = sizeof(uint32_t) * 4 * d.G;
-  k_ob_count<<<nchunk, 256, lds, e->stream>>>(d, ccnt);
-  k_ob_scan<<<1, 256, 0, e->stream>>>(d, ccnt, nchunk, off, e->ob_counts);
-  k_ob_fill<<<nchunk, 256, lds, e->stream>>>(d, off, e->ob_entries);
+  outbox_plan(e);
   // one block at least: block 0 checks every destination's packets against its plan bound
   k_outbox_pack_planned<<<(unsigned)(slots ? slots : 1), 64, 0, e->stream>>>(d, e->ob_entries, e->ob_counts, e->xbound, (uint8_t *)buf);
   e->n_ob = 0;
@@ -2222,14 +2216,10 @@ int gx_ae_pack(gx_engine *e, void *buf, uint64_t cap) {
   if (!e->n_pack) return GX_OK;
   if (e->ae_planned_round != (int)e->d.round || cap < e->n_pack * dig_bytes(e)) return GX_EINVAL;
   HIPCHK(hipSetDevice(e->device));
-  if (e->d.R % 2 == 0)
-    k_ae_digest<true><<<e->n_pack, 256, 0, e->stream>>>(e->d, e->ae_pack_host, e->ae_pack_t, e->ae_pack_other,
-                                                         e->ae_pack_first, (uint8_t *)buf,
-                                                         e->ae_dig, e->nblk, e->ae_bcnt);
-  else
-    k_ae_digest<false><<<e->n_pack, 256, 0, e->stream>>>(e->d, e->ae_pack_host, e->ae_pack_t, e->ae_pack_other,
-                                                          e->ae_pack_first, (uint8_t *)buf,
-                                                          e->ae_dig, e->nblk, e->ae_bcnt);
+  with_flag(vec_of(e), [&](auto V) {
+    k_ae_digest<V()><<<e->n_pack, 256, 0, e->stream>>>(e->d, e->ae_pack_host, e->ae_pack_t, e->ae_pack_other,
+                                                        e->ae_pack_first, (uint8_t *)buf, e->ae_dig, e->nblk, e->ae_bcnt);
+  });
   return phase_done(e);
 }
 
@@ -2283,7 +2273,7 @@ int gx_ae_delta_pack(gx_engine *e, void *buf, uint64_t cap) {
   if (!e->n_pack) return GX_OK;
   if (e->ae_delta_round != (int)e->d.round || cap < e->delta_total) return GX_EINVAL;
   HIPCHK(hipSetDevice(e->device));
-  if (e->nblk <= XS_MAXB)  // offsets up front, a wave per block (profiles/ab_shard_ae.sh)
+  if (ae_wave_blocks(e))
     k_ae_lead_pack_w<<<e->n_pack, 256, 0, e->stream>>>(e->d, e->ae_pack_host, e->ae_pack_t, e->ae_mask, e->ae_cnt,
                                                         e->ae_off, e->nmw, (const ulonglong2 *)e->ae_dig, e->nblk,
                                                         (uint8_t *)buf);
@@ -2305,7 +2295,7 @@ int gx_ae_return_bytes(gx_engine *e, const void *lead, uint64_t lead_bytes, uint
   const uint32_t np = e->n_pack;
   if (d.G < 2 || !ae_round(e) || !np) return lead_bytes ? GX_EINVAL : GX_OK;
   if (e->ae_delta_round != (int)d.round || lead_bytes != e->lead_in_total) return GX_EINVAL;
-  if (e->nblk <= XS_MAXB)
+  if (ae_wave_blocks(e))
     k_ae_ret_w<true><<<np, 256, 0, e->stream>>>(d, e->ae_pack_host, e->ae_pack_t, e->ae_fmask, e->ae_nfol, e->ae_lt,
                                                 (const uint8_t *)lead, e->ae_off + np, e->nblk, e->nmw,
                                                 e->ae_sz + 2 * np, nullptr, nullptr, nullptr, e->ae_retL);
@@ -2342,7 +2332,7 @@ int gx_ae_return_pack(gx_engine *e, const void *lead, uint64_t lead_bytes, void 
   if (!np) return GX_OK;
   if (e->ae_ret_round != (int)e->d.round || cap < e->ret_total || lead_bytes != e->lead_in_total) return GX_EINVAL;
   HIPCHK(hipSetDevice(e->device));
-  if (e->nblk <= XS_MAXB)
+  if (ae_wave_blocks(e))
     k_ae_ret_w<false><<<np, 256, 0, e->stream>>>(e->d, e->ae_pack_host, e->ae_pack_t, e->ae_fmask, e->ae_nfol,
                                                  e->ae_lt, (const uint8_t *)lead, e->ae_off + np, e->nblk, e->nmw,
                                                  e->ae_sz + 2 * np, e->ae_off + 2 * np, e->ae_off + 3 * np,
@@ -2378,15 +2368,7 @@ static void ae_plan_launch(gx_engine *e, uint32_t lo, uint32_t hi, const void *l
   // fewer than 4 pairs per CU: per-block bandwidth decides (2 tiles in flight measured slower for
   // the cross pairs of a post-heal round: 8.2 -> 9.3 ms at G = 2, H = 16384)
   const bool small = hi - lo < 1024;
-#define GX_AE_PLAN(V, E)                                                                                     \
-  (E ? k_ae_plan_ev<V> : small ? k_ae_plan_pf2<V> : k_ae_plan<V>)<<<hi - lo, 256, 0, st>>>(                    \
-      e->d, e->ae_pa + lo, e->ae_pb + lo, e->ae_prow + lo, e->ae_pcount + lo, in, e->ae_skip)
-  const bool ev = !e->log_views.empty();
-  if (e->d.R % 2 == 0 && !ev) GX_AE_PLAN(true, false);
-  else if (e->d.R % 2 == 0) GX_AE_PLAN(true, true);
-  else if (!ev) GX_AE_PLAN(false, false);
-  else GX_AE_PLAN(false, true);
-#undef GX_AE_PLAN
+  launch_ae_plan(e, small, hi - lo, st, e->ae_pa + lo, e->ae_pb + lo, e->ae_prow + lo, e->ae_pcount + lo, in, e->ae_skip);
 }
 
 int gx_ae_merge_local(gx_engine *e) {
@@ -2458,8 +2440,7 @@ int gx_lock_census(gx_engine *e, uint32_t *unlocked) {
   uint32_t *dv = (uint32_t *)e->api_dev;
   HIPCHK(hipMemsetAsync(dv, 0, sizeof(uint32_t), e->stream));
   if (e->d.Hl) k_lock_census<<<nblk(e->d.Hl, 256), 256, 0, e->stream>>>(e->d, dv);
-  HIPCHK(hipMemcpyAsync(unlocked, dv, sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
-  return sync_check(e);
+  return read_back(e, dv, unlocked);
 }
 
 // A push-pull round in which every host of the cluster holds the lock (the caller's collective

@@ -2110,6 +2110,10 @@ GXD void send_host(const Dev &d, Acc &a, uint32_t idx, gx_job *pjs, int do_bt, u
 // state except the receivers' inbox counts, zeroed a round ahead (Dev::in_cnt_nx).
 template <int T, bool X, bool SCAN = false, bool VEC = false, bool EV = false, int OWN = 0, bool PLAN = false>
 __global__ __launch_bounds__(256) void k_send(Dev d, int do_bt) {
+  // the variants the host builds (launch_send): VEC, EV and OWN only shape the scans and owner ticks
+  // that SCAN brings in, and planned sends run without departures or the detector
+  static_assert(SCAN || (!VEC && !EV && OWN == 0), "k_send: VEC, EV and OWN need SCAN");
+  static_assert(!(PLAN && X), "k_send: PLAN runs without departures or the detector (X)");
   __shared__ gx_job s_pj[256 / T][T * GX_JPF];  // FIFO head jobs of the block's hosts, loaded ahead
   // send_planned's chunk plans, then the team's peers (16 u32 = one PlanCall's 64 B)
   __shared__ PlanCall s_pl[PLAN ? 256 / T : 1][PLAN_CH + 1];
