@@ -298,11 +298,21 @@ typedef struct gx_params {
    * (ServiceMsgs 25 + the blocked AddServiceEntry), and merge at the start of the receive phase of
    * the host's first unlocked round, before its pipeline (an unpinned order: the reference
    * interleaves the two blocked senders). The engine keeps the partner's pre-exchange state in a
-   * pool of lock_defer_slots rows per engine: host v uses slot v % lock_defer_slots. When the slot
-   * is taken, the merge is dropped and counted (gx_stats.ae_defer_lost); a run is faithful while
-   * that stays 0. Of several hosts claiming one free slot in a round (or push-pull batch), the
-   * lowest host id gets it. 0 (default) = every exchange with a locked side fails, the round-5
-   * model. Unsharded engines only (GX_EINVAL otherwise). lock_defer_slots: 1..4096 (0 = 64). */
+   * pool of lock_defer_slots rows per engine (lock_defer_slots * n_hosts * n_services * 8 bytes). A
+   * merge that gets no slot is dropped and counted (gx_stats.ae_defer_lost); a run is faithful
+   * while that stays 0. Two pool policies:
+   *   lock_readers = 1, direct-mapped: host v uses slot v % lock_defer_slots, and its merge is
+   *     dropped when another host holds that slot, whatever else is free. Of several hosts claiming
+   *     one free slot in a round (or push-pull batch), the lowest host id gets it.
+   *   lock_readers = 2, claimed (the HIP engine only; the oracle answers GX_EINVAL): at each
+   *     push-pull launch (a matching round, or one GX_PP_INITIATE batch) the read-locked sides of the
+   *     launch's exchanges, in ascending host id, take the slots free at the launch's start, in
+   *     ascending slot index: the k-th claimant gets the k-th free slot, and a merge is dropped only
+   *     when every slot is taken. When an exchange runs, what the unlocked side does, when the
+   *     waiting merge runs and what it holds of the pipeline are as with 1; with lock_defer_slots = 1
+   *     the two policies are the same, and while neither loses a merge they give the same run.
+   * 0 (default) = every exchange with a locked side fails, the round-5 model. Unsharded engines
+   * only (GX_EINVAL otherwise). lock_defer_slots: 1..4096 (0 = 64). */
   uint32_t lock_readers;
   uint32_t lock_defer_slots;
   /* lock_model = 1 with fd_enable, unsharded engines: memberlist's own alive / suspect / dead

@@ -30,6 +30,9 @@ JOB_NIL_BS, JOB_NIL_BT, JOB_RETX, JOB_SEND, JOB_EXPIRE, JOB_LOST = 0, 1, 2, 3, 4
 INIT_EMPTY, INIT_OWN, INIT_WARM = 0, 1, 2
 LIMIT_DEFAULT = 0xFFFFFFFF
 LOCK_PENDING_EXPIRE, LOCK_DEFER_MERGE, LOCK_BUF_SHIFT = 4, 8, 8  # gx_host_state.lock (gx.h)
+# gx_params.lock_readers (gx.h): the waiting merges' pool is direct-mapped (slot v % lock_defer_slots)
+# or claimed from a free list (HIP engine only)
+LOCK_READERS_OFF, LOCK_READERS_MAPPED, LOCK_READERS_CLAIMED = 0, 1, 2
 
 K_NAMES = ["owner", "scan", "storm", "send", "route", "merge", "ae", "converge", "encode", "decode", "fd"]
 

@@ -185,14 +185,20 @@ struct Dev {
   uint32_t *pexp;      // [Hl][PW] owners whose ExpireServer waits for the host's lock
   int in_round;        // a round phase is running: ExpireServer waits for the lock (ABI calls act directly)
   // gx.h lock_readers: push-pull merges of read-locked hosts waiting for their lock, in a pool of P
-  // rows (host v uses slot v % P); each slot's host (GX_NOHOST = free), the pipeline places its merge
-  // holds and the lowest claimant of the current batch. ro_flag[t]: pair t of the last push-pull
+  // rows (host v uses slot v % P, or dslot[v] below); each slot's host (GX_NOHOST = free), the
+  // pipeline places its merge holds and the lowest claimant of the current batch. ro_flag[t]: pair t of the last push-pull
   // launch runs with a read-locked side (k_ae_ro takes it); ro_list: k_ae_ro's ordered list.
   uint32_t P;
   uint64_t *dpool;     // [P][R]
   uint32_t *dpool_host, *dpool_res, *dclaim;  // [P]
   uint8_t *ro_flag;    // [H]
   uint32_t *ro_list;   // [H]
+  // lock_readers = 2 (the claimed pool): slots come from a free list, so host v's slot is dslot[v]
+  // (GX_NOHOST = no merge waits); claim_bits: the read-locked sides of the launch being claimed for,
+  // one bit per host (k_ae_claim sets and clears them); ro_n: the length of ro_list (k_ae_rox).
+  uint32_t *dslot;       // [H]
+  uint32_t *claim_bits;  // [ceil(H / 32)]
+  uint32_t *ro_n;        // [1]
   // gx.h fd_handoff_shared: memberlist messages waiting in each host's handoff queue (HQ places per
   // host, count gx_fd_host.hq_len), arrival order
   uint32_t HQ;
@@ -437,6 +443,7 @@ GXD uint32_t lock_snap(uint32_t lockw, uint32_t flags, int64_t round, bool rw) {
 // lock did not hold it at the round's start and no writer waits (no record in the pipeline, no
 // waiting ExpireServer or merge, no BroadcastTombstones tick due). Oracle: ro_side.
 #define GX_NOHOST 0xffffffffu
+#define GX_LOCK_READERS_CLAIMED 2u  // gx.h lock_readers = 2: pool slots claimed from a free list
 GXD bool ro_side(const Dev &d, uint32_t v) {
   const gx_host_state *h = hst(d, v);
   const uint32_t lw = gld(&h->lock);
@@ -451,7 +458,10 @@ GXD bool ro_pair(const Dev &d, uint32_t a, uint32_t b) {
 // holds min(n, 26) of its places (gx.h GX_LOCK_DEFER_RES). Oracle: pipe_cap.
 GXD uint32_t pipe_cap(const Dev &d, uint32_t vi, uint32_t lw) {
   if (!(lw & GX_LOCK_DEFER_MERGE)) return d.C;
-  const uint32_t res = d.dpool_res[(d.lo + vi) % d.P];
+  uint32_t slot = (d.lo + vi) % d.P;
+  if (d.p.lock_readers == GX_LOCK_READERS_CLAIMED) slot = d.dslot[d.lo + vi];  // set before the DEFER bit
+  if (slot >= d.P) return d.C;
+  const uint32_t res = d.dpool_res[slot];
   return d.C > res ? d.C - res : 0u;
 }
 GXD void note_locked(const Dev &d) { atomicMin(&d.ctr->first_drop[shard_id()][1], (unsigned long long)d.round); }

@@ -3924,6 +3924,127 @@ __global__ __launch_bounds__(256) void k_ae_ro(Dev d, const uint32_t *pa, const 
   }
   for (uint32_t x = tid; x < d.P; x += blockDim.x) d.dclaim[x] = GX_NOHOST;  // (3)
 }
+// gx.h lock_readers = 2, the claimed pool: k_ae_ro's work in two launches. k_ae_claim (one block,
+// after the push-pull launch and its membership half) hands out the pool's slots: the claimants are
+// the read-locked sides of the flagged pairs, the free slots those free now (no slot is freed before
+// the next round's drain); in ascending host id the k-th claimant takes the k-th free slot in
+// ascending slot index (dslot[x], dpool_host[slot]), and a claimant past the last free slot is lost
+// (its dslot stays GX_NOHOST). With one slot this is k_ae_ro's rule, the lowest host id gets it.
+// It also writes the flagged pairs in pair order (ro_list, *ro_n) for k_ae_rox and clears ro_flag.
+// Three ordered block scans: the pairs per thread range, the free slots, the claimants' bitmap.
+#define GX_POOL_MAX 4096  // gx.h lock_defer_slots' bound (gx_create checks it)
+__global__ __launch_bounds__(256) void k_ae_claim(Dev d, const uint32_t *pa, const uint32_t *pb, uint64_t key0,
+                                                  uint64_t key1, uint32_t n) {
+  __shared__ unsigned long long s_wave[4];
+  __shared__ uint16_t s_free[GX_POOL_MAX];
+  const uint32_t tid = threadIdx.x, per = (n + 255) / 256, t0 = tid * per < n ? tid * per : n;
+  const uint32_t t1 = t0 + per < n ? t0 + per : n;
+  uint32_t c = 0;
+  for (uint32_t t = t0; t < t1; t++) c += d.ro_flag[t] != 0;
+  unsigned long long tot;
+  uint32_t pos = (uint32_t)block_excl_scan64(c, s_wave, tot);  // threads hold consecutive ranges: pair order
+  for (uint32_t t = t0; t < t1; t++) {
+    if (!d.ro_flag[t]) continue;
+    d.ro_list[pos++] = t;
+    d.ro_flag[t] = 0;
+    uint32_t a, b;
+    if (pa) {
+      a = pa[t];
+      b = pb[t];
+    } else {
+      ae_pair_hosts(d, t, key0, key1, a, b);
+    }
+    if (host_locked(d, a)) atomicOr(&d.claim_bits[a >> 5], 1u << (a & 31));
+    if (host_locked(d, b)) atomicOr(&d.claim_bits[b >> 5], 1u << (b & 31));
+  }
+  if (tid == 0) *d.ro_n = (uint32_t)tot;
+  if (!tot) return;  // block-uniform: no flagged pair, no bit set
+  uint32_t nfree = 0;
+  for (uint32_t s0 = 0; s0 < d.P; s0 += 256) {  // the free slots, ascending
+    const uint32_t s = s0 + tid;
+    const bool f = s < d.P && d.dpool_host[s] == GX_NOHOST;
+    const uint32_t at = nfree + (uint32_t)block_excl_scan64(f, s_wave, tot);
+    if (f) s_free[at] = (uint16_t)s;
+    nfree += (uint32_t)tot;
+  }
+  __syncthreads();  // s_free; and every claimant's bit is set (the atomics are done at the barrier)
+  const uint32_t nw = (d.H + 31) / 32;
+  uint32_t base = 0;
+  for (uint32_t w0 = 0; w0 < nw; w0 += 256) {  // the claimants, ascending: rank = set bits below
+    const uint32_t w = w0 + tid;
+    uint32_t bits = w < nw ? atomicExch(&d.claim_bits[w], 0u) : 0u;  // read at the L2, and cleared
+    uint32_t k = base + (uint32_t)block_excl_scan64((unsigned long long)__popc(bits), s_wave, tot);
+    for (; bits; bits &= bits - 1u, k++) {
+      if (k >= nfree) break;  // lost, with every higher claimant
+      const uint32_t x = 32u * w + (uint32_t)__ffs(bits) - 1u, slot = s_free[k];
+      d.dslot[x] = slot;
+      d.dpool_host[slot] = x;
+    }
+    base += (uint32_t)tot;
+  }
+  if (tid == 0 && base > nfree) ctr_atomic(d, C_AE_DEFER_LOST, base - nfree);
+}
+// ... and k_ae_rox runs the flagged pairs, blocks striding over ro_list (the pairs are disjoint, and
+// no slot serves two hosts): a read-locked side with a slot keeps the partner's pre-exchange row there
+// (16-B loads and stores on even rows) before any merge of the pair and holds min(n, 26) pipeline
+// places, one without a slot lost its merge (k_ae_claim counted it); then the unlocked side merges
+// the partner's row, as in k_ae_ro.
+template <bool VEC, bool EV>
+__global__ __launch_bounds__(256) void k_ae_rox(Dev d, const uint32_t *pa, const uint32_t *pb, uint64_t key0,
+                                                uint64_t key1) {
+  __shared__ unsigned long long s_wave[4];
+  __shared__ unsigned long long s_red[4];
+  const uint32_t tid = threadIdx.x, nro = *d.ro_n;
+  for (uint32_t k = blockIdx.x; k < nro; k += gridDim.x) {  // block-uniform
+    const uint32_t t = d.ro_list[k];
+    uint32_t a, b;
+    if (pa) {
+      a = pa[t];
+      b = pb[t];
+    } else {
+      ae_pair_hosts(d, t, key0, key1, a, b);
+    }
+    const bool la = host_locked(d, a), lb = host_locked(d, b);
+    __syncthreads();  // every thread has read the lock words before a side's DEFER bit is set
+    for (int q = 0; q < 2; q++) {
+      const uint32_t x = q ? b : a, y = q ? a : b;
+      if (!(q ? lb : la)) continue;
+      const uint32_t slot = d.dslot[x];
+      if (slot >= d.P) continue;  // no slot was free: the merge is lost
+      const uint64_t *src = vrow(d, y);
+      uint64_t *dst = &d.dpool[(size_t)slot * d.R];
+      unsigned long long np = 0;
+      if (VEC) {
+        typedef unsigned long long v2u64s __attribute__((ext_vector_type(2)));
+#pragma unroll 4
+        for (uint32_t r = 2 * tid; r < d.R; r += 2 * blockDim.x) {
+          const ulonglong2 w = ld16<false>(&src[r]);  // the partner's merge reads the row again
+          __builtin_nontemporal_store((v2u64s){w.x, w.y}, reinterpret_cast<v2u64s *>(&dst[r]));
+          np += (st_of(w.x) != GX_ABSENT) + (st_of(w.y) != GX_ABSENT);
+        }
+      } else {
+        for (uint32_t r = tid; r < d.R; r += blockDim.x) {
+          const uint64_t w = src[r];
+          dst[r] = w;
+          np += st_of(w) != GX_ABSENT;
+        }
+      }
+      np = block_sum(np, s_red);
+      if (tid == 0) {
+        d.dpool_res[slot] = np < GX_LOCK_DEFER_RES ? (uint32_t)np : GX_LOCK_DEFER_RES;
+        hst(d, x)->lock |= GX_LOCK_DEFER_MERGE;
+        ctr_atomic(d, C_AE_DEFER, 1);
+        kbytes(d, GX_K_AE, 16ull * d.R, 0);
+      }
+    }
+    __threadfence();
+    __syncthreads();
+    if (!la) ae_pair<VEC, 1, false, EV>(d, a, b, false, s_wave, s_red);  // the unlocked side merges now
+    else if (!lb) ae_pair<VEC, 1, false, EV>(d, b, a, false, s_wave, s_red);
+    if (tid == 0) ctr_atomic(d, C_AEX, 1);
+    __syncthreads();
+  }
+}
 // gx.h lock_readers: the waiting merge of pool slot s's host at the receive phase of the host's
 // first unlocked round, before its pipeline and this round's packets (k_merge_seg runs after): the
 // kept row through Merge in key order (ae_pair from the pool row, SRC_AE). Oracle: run_deferred_merge.
@@ -3941,6 +4062,7 @@ __global__ __launch_bounds__(256) void k_defer_drain(Dev d) {
   if (threadIdx.x == 0) {
     d.dpool_host[s] = GX_NOHOST;
     d.dpool_res[s] = 0;
+    if (d.dslot) d.dslot[x] = GX_NOHOST;  // the claimed pool (lock_readers = 2)
     d.hs[vi].lock = lw & ~GX_LOCK_DEFER_MERGE;
     d.tick[vi] = 2;
   }
