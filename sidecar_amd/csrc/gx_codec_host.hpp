@@ -538,6 +538,7 @@ int gx_merge_remote_state_json(gx_engine *e, uint32_t view, const char *buf, uin
   if (!e || !own(e, view) || (len && !buf)) return GX_EINVAL;
   if (!e->codec) return GX_ENOENT;
   HIPCHK(hipSetDevice(e->device));
+  quiet_invalidate(e);
   gxc::Dec x;
   uint32_t n = 0;
   int rc = dec_impl(e, buf, len, ds, x, n);

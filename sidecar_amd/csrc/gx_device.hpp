@@ -143,7 +143,8 @@ struct Dev {
   uint4 *in_hdr;       // [Hl][DI] {global key = sender * K + j, entry, len, slot}, arrival order
   uint4 *in_ovf;       // [H*K] {key, entry, len, local receiver} past a receiver's DI slots
   grec *in_rec;        // [Hl][DR][packet_cap] records of a receiver's first DR packets
-  uint32_t *work_cnt;  // [0..1] expiry-scan worklist, [2..3] overflow list counts by round parity, [4] error bits
+  uint32_t *work_cnt;  // [0..1] expiry-scan worklist, [2..3] overflow list counts by round parity, [4] error bits,
+                       // [5] scanned views (GX_WC_*)
   uint32_t *wl_cnt, *wl_cnt_nx;    // this / next round's worklist count (into work_cnt)
   uint32_t *ovf_cnt, *ovf_cnt_nx;  // this / next round's overflow-list count
   uint32_t *work;      // [Hl] views whose expiry scan must stream the row this round
@@ -176,7 +177,13 @@ struct Dev {
   uint32_t logS;       // log2(S) when S is a power of two
   int departures;      // p.depart_round >= 0 && p.depart_ppm
   uint32_t nblk_ae;    // digest blocks per row, ceil(R / GX_DIGEST_SLOTS)
-  uint64_t *snap;      // this round's k_send stores (round << 32 | work_cnt[GX_WC_SCANS]) here (pinned host memory), or null
+  uint64_t *snap;      // this round's k_send stores (snap_tag << 32 | value) here (pinned host memory), or null
+  uint32_t snap_tag, snap_word;  // the value: work_cnt[snap_word], or the last round's quiet bound (GX_SNAP_QUIET)
+  // [2][QW] the quiet-round terms of k_send's waves by round parity (quiet_term; QW = 4 waves per block):
+  // the minimum of round n's is the bound B such that every round in [n + 1, B) is quiet. Every wave
+  // stores its own word each round, so nothing is reset and no two waves meet on one address.
+  uint32_t *quiet_w;
+  uint32_t QW;
   uint32_t sfilt;      // senders pre-filter inbound records for their local receivers (1 shard; see k_send)
   // the ServicesState lock held by a blocked looper (gx.h lock_model)
   uint32_t C;          // lock_buffer: records a locked host's inbound pipeline holds
@@ -302,6 +309,14 @@ GXD unsigned long long wave_min(unsigned long long x) {
   return x;
 }
 
+GXD uint32_t wave_min32(uint32_t x) {
+  for (int o = 32; o > 0; o >>= 1) {
+    const uint32_t y = (uint32_t)__shfl_xor((int)x, o, 64);
+    x = y < x ? y : x;
+  }
+  return x;
+}
+
 // Per-thread event counts; flushed once per wave (all 64 lanes must call acc_flush).
 struct Acc {
   unsigned c[C_NCTR];
@@ -355,6 +370,7 @@ GXD void wave_sync() {
 #define GX_WC_ERR 4
 #define GX_WC_SCANS 5  // work_cnt[5]: views streamed by expiry scans so far (wraps; differences only)
 #define GX_WC_N 8
+#define GX_SNAP_QUIET 0xffffffffu  // Dev::snap_word: the snapshot is the minimum of the last round's Dev::quiet_w
 // Register a packet (global sender key, message entry) in local receiver vi's inbox: one atomic
 // on the receiver's count; returns the inbox position (slot). The header itself (with the record
 // count) is written by inbox_header once the packet is packed.
@@ -463,6 +479,31 @@ GXD uint32_t pipe_cap(const Dev &d, uint32_t vi, uint32_t lw) {
   if (slot >= d.P) return d.C;
   const uint32_t res = d.dpool_res[slot];
   return d.C > res ? d.C - res : 0u;
+}
+// Quiet rounds: a round is quiet when, at its start, every local host holds the lock
+// for it and its inbound pipeline is full, so no receiver appends, merges or drains anything and no
+// push-pull pair runs. Host vi's term, from its bookkeeping `hs` as round d.round's GetBroadcasts
+// calls leave it (lock word already written for d.round + 1): the first round >= d.round + 1 for
+// which this host may stop being locked with a full pipeline, or 0 when it is not so in round
+// d.round + 1 already. The host stays locked while a looper flag is set; a flag clears only when
+// fifo_head passes that looper's nil (pop_job_r), a round dequeues at most KG jobs (one per
+// GetBroadcasts call of send_planned), jobs pushed later queue behind the nil and new flags only add
+// locks; so with D = max over the set flags of (nil_pos - fifo_head) + 1 dequeues to go, the host is
+// locked in every round of [d.round + 1, d.round + 1 + ceil(D / KG)). Its pipeline count changes only
+// by an append (needs room) or a drain (needs an unlocked round): full and locked in round d.round
+// (so this round's receive phase, which runs after this, neither appends nor drains), it stays full
+// while the host stays locked. The minimum over the hosts bounds the quiet rounds.
+GXD uint32_t quiet_term(const Dev &d, uint32_t vi, const gx_host_state &hs) {
+  const uint32_t lw = hs.lock;
+  if (!(hs.flags & 3u) || !locked_in(d, lw) || !GX_LOCK_AT(lw, d.round + 1)) return 0u;
+  if (GX_LOCK_BUF(lw) < pipe_cap(d, vi, lw)) return 0u;
+  uint32_t dist = 0;
+  if (hs.flags & 1u) dist = hs.nil_pos_bs - hs.fifo_head;
+  if ((hs.flags & 2u) && hs.nil_pos_bt - hs.fifo_head > dist) dist = hs.nil_pos_bt - hs.fifo_head;
+  if (dist >= hs.fifo_tail - hs.fifo_head) return 0u;  // (cannot happen: a blocked looper's nil is queued)
+  const uint32_t kg = d.KG ? d.KG : 1u;
+  const uint64_t b = (uint64_t)d.round + 1u + (dist + kg) / kg;  // ceil((dist + 1) / kg)
+  return b < 0xfffffffeull ? (uint32_t)b : 0xfffffffeu;
 }
 GXD void note_locked(const Dev &d) { atomicMin(&d.ctr->first_drop[shard_id()][1], (unsigned long long)d.round); }
 

@@ -29,8 +29,10 @@
 #include <string.h>
 
 #include <algorithm>
+#include <chrono>
 #include <deque>
 #include <string>
+#include <thread>
 #include <type_traits>
 #include <vector>
 
@@ -60,6 +62,11 @@ struct TimedLaunch {
   hipEvent_t a, b;
 };
 
+// Quiet-round bounds asked for and not stored yet, one every second round: with all of them
+// outstanding the host is 8 rounds ahead of the device and lets it catch up (quiet_probe). 8 rounds
+// are 250 us of queued work at cfg 5; the shortest quiet stretches of the test schedules are 10.
+#define GX_QUIET_SLOTS 4
+
 struct gx_engine {
   Dev d;
   hipStream_t stream;      // where all device work goes (own_stream, or the caller's: gx_set_stream)
@@ -77,10 +84,21 @@ struct gx_engine {
   // memory every second round and consumed two snapshots later (scan_probe_begin). Both placements give
   // the same results; only the time differs.
   bool scan_heavy;
-  uint64_t *scan_snap;      // [2] pinned host copies of (round << 32 | work_cnt[GX_WC_SCANS]), written by k_send
+  uint64_t *scan_snap;      // [2 + GX_QUIET_SLOTS] pinned host copies of (tag << 32 | a work_cnt word), written by
+                            // k_send: [0..1] work_cnt[GX_WC_SCANS] tagged with the round, then quiet-round
+                            // bounds (quiet_probe)
   uint64_t *scan_snap_dev;  // the same memory as the device addresses it
   uint32_t scan_tag[2];     // the round each slot's snapshot was asked for
   uint32_t scan_k, scan_last;
+  // Quiet rounds (quiet_round): every round from now until quiet_until is quiet, by the
+  // bounds the device has reported through scan_snap[2..]. quiet_tag: the snapshot each slot was asked
+  // for and has not shown yet (0 = none; tags are never reused, so a snapshot from before an
+  // invalidation is ignored); quiet_from: no bound folded before this round counts
+  // (quiet_invalidate); quiet_now: this round takes the quiet path.
+  uint32_t quiet_tag[GX_QUIET_SLOTS], quiet_seq;
+  bool quiet_nowait;  // a bound took too long in this gx_run_rounds call: no more polling in it
+  int64_t quiet_until, quiet_from;
+  bool quiet_now;
   uint32_t *in_cnt_buf;     // [2][Hl] inbox counts by round parity (Dev::in_cnt, in_cnt_nx)
   int async_phases;         // sharded phase calls return without waiting (gx_set_stream)
   int device;
@@ -377,6 +395,8 @@ static void owner_launch(const Dev &d, hipStream_t s) {
 static int scan_probe_begin(gx_engine *e) {
   e->d.snap = nullptr;
   if (e->d.round % 2) return GX_OK;
+  e->d.snap_tag = (uint32_t)e->d.round;
+  e->d.snap_word = GX_WC_SCANS;
   const uint32_t i = e->scan_k & 1u;
   if (e->scan_k >= 2) {
     const uint64_t v = __atomic_load_n(&e->scan_snap[i], __ATOMIC_ACQUIRE);
@@ -391,9 +411,88 @@ static int scan_probe_begin(gx_engine *e) {
 }
 static int scan_probe_end(gx_engine *e) {
   if (!e->d.snap) return GX_OK;
-  e->scan_k++;
+  if (e->d.snap < &e->scan_snap_dev[2]) e->scan_k++;  // (not quiet_probe's)
   e->d.snap = nullptr;
   return GX_OK;
+}
+
+// The parameters under which quiet rounds are predicted (quiet_term's argument): one engine, the lock
+// modelled without read-locked exchanges, no detector, departures or shared handoff queue, one
+// GetBroadcasts call per target and none outside k_send (probe_piggyback), planned sends (they count
+// a full pipeline's drops at plan time and register nothing).
+static bool quiet_params(const Dev &d) {
+  return d.G == 1 && d.K && d.p.lock_model == 1 && !d.p.lock_readers && !d.p.fd_enable && !d.departures &&
+         !d.p.fd_handoff_shared && d.NG == 1 && !d.p.probe_piggyback && !d.p.limit_bytes && d.p.retransmit_rounds > 0;
+}
+// The bounds the device has stored by now (scan_snap[2..], each tagged as asked); returns a free
+// slot or -1.
+static int quiet_take(gx_engine *e) {
+  int free_slot = -1;
+  for (int i = GX_QUIET_SLOTS - 1; i >= 0; i--) {
+    if (e->quiet_tag[i]) {
+      const uint64_t v = __atomic_load_n(&e->scan_snap[2 + i], __ATOMIC_ACQUIRE);
+      if ((uint32_t)(v >> 32) != e->quiet_tag[i]) continue;
+      e->quiet_tag[i] = 0;
+      if ((int64_t)(uint32_t)v > e->quiet_until) e->quiet_until = (int64_t)(uint32_t)v;
+    }
+    free_slot = i;
+  }
+  return free_slot;
+}
+// The other rounds (after scan_probe_begin left Dev::snap free): takes the bounds asked for earlier
+// that the device has stored by now, and asks this round's k_send for the bound the last round's
+// k_send finished (the minimum of its waves' terms, Dev::quiet_w; valid from this round on).
+// The host's lead is bounded here: a bound helps only while it reaches past the round the host is
+// queueing, and left alone the host queues a whole gx_run_rounds call before the device has run its
+// first rounds (measured: no round of a 150-round call took the quiet path). With every slot
+// outstanding the host is 2 * GX_QUIET_SLOTS rounds ahead, and it polls the slots until the oldest
+// bound arrives. gx_run_rounds returns only when the device is done, so the call takes no longer
+// while those rounds keep the device's queue filled. A bound that takes more than GX_QUIET_WAIT_MS
+// (a stuck device, a kernel of seconds) ends the polling for the rest of the call (quiet_nowait): a
+// late or missing bound only means the generic path.
+#define GX_QUIET_WAIT_MS 1000
+static void quiet_probe(gx_engine *e) {
+  Dev &d = e->d;
+  int free_slot = quiet_take(e);
+  if (d.snap || d.round <= e->quiet_from) return;
+  if (free_slot < 0 && !e->quiet_nowait) {
+    const auto deadline = std::chrono::steady_clock::now() + std::chrono::milliseconds(GX_QUIET_WAIT_MS);
+    while ((free_slot = quiet_take(e)) < 0) {
+      if (std::chrono::steady_clock::now() > deadline) {
+        e->quiet_nowait = true;
+        break;
+      }
+      std::this_thread::yield();
+    }
+  }
+  if (free_slot < 0) return;
+  if (!++e->quiet_seq) ++e->quiet_seq;
+  e->quiet_tag[free_slot] = e->quiet_seq;
+  d.snap = &e->scan_snap_dev[2 + free_slot];
+  d.snap_tag = e->quiet_seq;
+  d.snap_word = GX_SNAP_QUIET;
+}
+// Every ABI entry that can change device state between rounds calls this (gx_run_rounds itself does
+// not): what the device reported, or still reports, about rounds before the call no longer counts.
+// Callers: gx_set_stream, gx_set_round, api_add (gx_add_service_entries, gx_notify_msg,
+// gx_merge_remote_state), gx_merge, gx_tombstone_others, gx_tombstone_services, gx_expire_server
+// (gx_notify_leave), gx_send_services, gx_broadcast_services, gx_broadcast_tombstones,
+// gx_get_broadcasts / gx_get_broadcasts_bytes (getb_impl), gx_set_static_bytes, gx_add_listener,
+// gx_remove_listener, gx_notify_msgs (through gx_notify_msg), gx_write_views, gx_write_slot, and the
+// phase calls an unsharded engine accepts: gx_round_send (gx_round_gossip_begin), gx_round_merge
+// (gx_round_gossip_end), gx_ae_merge, gx_round_end, and gx_merge_remote_state_json
+// (gx_codec_host.hpp). The memberlist calls (gx_fd_*) and the other
+// sharded phase calls need fd_enable or more than one shard, which quiet_params excludes.
+static void quiet_invalidate(gx_engine *e) {
+  memset(e->quiet_tag, 0, sizeof(e->quiet_tag));
+  e->quiet_until = 0;
+  e->quiet_from = e->d.round;  // the round that runs next folds the first bound that counts
+}
+// Whether round d.round skips its receive phase (run_one_round) and its push-pull pairs
+// (ae_whole_impl): a bound reported by the device covers it. The storm's round and rounds with a
+// listener stay on the generic path (no test covers them quiet; nothing to gain there).
+static bool quiet_round(const gx_engine *e, bool storm) {
+  return quiet_params(e->d) && !storm && e->log_views.empty() && e->d.round < e->quiet_until;
 }
 
 // k_send's variant. X: departures or the detector; SCAN: the round's expiry scans run in k_send's
@@ -432,6 +531,7 @@ static int round_send_impl(gx_engine *e) {
     int rc = scan_probe_begin(e);
     if (rc) return rc;
   }
+  if (quiet_params(d)) quiet_probe(e);
   d.n_remote = 0;
   hipStream_t s = e->stream;
   if (d.p.probe_piggyback) {  // the probe ping and ack calls come before the owner phase (gx.h)
@@ -454,6 +554,7 @@ static int round_send_impl(gx_engine *e) {
   // passes sleep; teams of 4 lanes per host
   const bool plan = !d.p.limit_bytes && d.p.retransmit_rounds > 0 && !d.departures && !d.p.fd_enable;
   const SendSel sel{d.p.fd_enable || d.departures, scan_in_send, plan, fused ? own_class(d.S) : 0};
+  e->quiet_now = quiet_round(e, storm);
   if (!fused) {
     LaunchTimer t(e, GX_K_OWNER);
     owner_launch(d, s);
@@ -666,7 +767,7 @@ static int ae_initiate(gx_engine *e) {
 }
 
 // Phase 5 on an unsharded engine: pairs derived on device.
-static int ae_whole_impl(gx_engine *e) {
+static int ae_whole_impl(gx_engine *e, bool quiet) {
   Dev &d = e->d;
   set_round_fields(e);
   hipStream_t s = e->stream;
@@ -685,7 +786,10 @@ static int ae_whole_impl(gx_engine *e) {
       np = d.H / 2;
       key0 = rng4(d.p.seed, ST_AE, (uint64_t)d.round, 0, 0);
     }
-    if (np) {
+    if (np && quiet) {  // every host holds the lock: each pair fails on it, the round is only its counts
+      LaunchTimer t(e, GX_K_AE);
+      k_ae_locked_note<<<1, 64, 0, s>>>(d, np, 1u);
+    } else if (np) {
       LaunchTimer t(e, GX_K_AE);
       // PF = 1: deeper prefetch measured within noise (profiles/ae_variants.sh)
       // the ChangeEvent variant only while some view has a listener
@@ -713,10 +817,14 @@ static int ae_whole_impl(gx_engine *e) {
   return GX_OK;
 }
 
+// A quiet round (quiet_round, decided in round_send_impl) has no receive phase: no inbox was written
+// and every pipeline is full and stays (k_lock_append and k_merge_seg would find nothing).
 static int run_one_round(gx_engine *e) {
   int rc = round_send_impl(e);
-  if (!rc) rc = round_merge_impl(e);
-  if (!rc) rc = ae_whole_impl(e);
+  const bool quiet = e->quiet_now;
+  e->quiet_now = false;
+  if (!rc && !quiet) rc = round_merge_impl(e);
+  if (!rc) rc = ae_whole_impl(e, quiet);
   if (!rc) e->d.round++;
   return rc;
 }
@@ -736,6 +844,7 @@ int gx_abi_version(void) { return GX_ABI_VERSION; }
 int gx_set_stream(gx_engine *e, void *stream, int mode) {
   if (!e || (mode & ~(GX_STREAM_CALLER | GX_STREAM_ASYNC))) return GX_EINVAL;
   HIPCHK(hipSetDevice(e->device));
+  quiet_invalidate(e);
   if (e->side_pending) HIPCHK(hipStreamSynchronize(e->side_stream));
   e->side_pending = false;
   HIPCHK(hipStreamSynchronize(e->stream));  // work queued so far completes first
@@ -883,7 +992,7 @@ int gx_destroy(gx_engine *e) {
   void *ptrs[] = {e->ae_dig, e->ae_mask, e->ae_fmask, e->ae_lt, e->ae_retL, e->ae_bcnt, e->ae_cnt, e->ae_nfol, e->ae_sz, e->ae_off, e->ae_rioff, e->ae_err, d.msg_key, d.in_stamp, e->ob_entries, e->ob_counts, e->ob_total, e->ob_claim, e->ae_pa, e->ae_pb, e->ae_pack_host, e->ae_pack_t, e->ae_pack_other, e->ae_pack_first, e->ae_skip, e->fd_rsnap, e->ae_prow,
                   e->ae_pcount, d.view, d.minexp, d.own_status, d.hs, d.fifo, d.sleep, d.dq, d.arena, d.arena_len, d.msg, d.msg_w0, d.msg_len,
                   d.msg_dst, e->in_cnt_buf, d.scan_list, d.scan_cnt, d.tick,
-                  d.sbytes, d.srvt, d.vlc, d.ev_slot, d.ev_log, d.ev_cnt, d.ctr, d.in_hdr, d.in_ovf, d.in_rec, d.work_cnt, d.work, d.mrec, e->pp_dev, e->pp_prow, e->name_rank, e->api_dev, e->conv_bad, e->digest_buf, d.kprof,
+                  d.sbytes, d.srvt, d.vlc, d.ev_slot, d.ev_log, d.ev_cnt, d.ctr, d.in_hdr, d.in_ovf, d.in_rec, d.work_cnt, d.quiet_w, d.work, d.mrec, e->pp_dev, e->pp_prow, e->name_rank, e->api_dev, e->conv_bad, e->digest_buf, d.kprof,
                   d.mem, d.fd_dl, d.fdh, d.fdm, d.fd_len, d.fd_peers, d.fd_np, d.fd_snap, d.lkb, d.pexp, d.dpool, d.dpool_host, d.dpool_res, d.dclaim, d.ro_flag, d.ro_list, d.dslot, d.claim_bits, d.ro_n, d.fdq};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
@@ -940,6 +1049,11 @@ int gx_create(const gx_params *p, gx_engine **out) {
   e->side_pending = false;
   e->scan_heavy = true;  // k_scan placement until the first snapshots say no view gets scanned
   e->scan_snap = e->scan_snap_dev = nullptr;
+  memset(e->quiet_tag, 0, sizeof(e->quiet_tag));
+  e->quiet_seq = 0;
+  e->quiet_nowait = false;
+  e->quiet_until = e->quiet_from = 0;
+  e->quiet_now = false;
   e->scan_tag[0] = e->scan_tag[1] = 0xffffffffu;
   e->scan_k = e->scan_last = 0;
   e->async_phases = 0;
@@ -1002,13 +1116,14 @@ int gx_create(const gx_params *p, gx_engine **out) {
   if (hipStreamCreateWithFlags(&e->side_stream, hipStreamNonBlocking) != hipSuccess ||
       hipEventCreateWithFlags(&e->side_start, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&e->side_done, hipEventDisableTiming) != hipSuccess ||
-      hipHostMalloc((void **)&e->scan_snap, 2 * sizeof(uint64_t), hipHostMallocMapped) != hipSuccess ||
+      hipHostMalloc((void **)&e->scan_snap, (2 + GX_QUIET_SLOTS) * sizeof(uint64_t), hipHostMallocMapped) != hipSuccess ||
       hipHostGetDevicePointer((void **)&e->scan_snap_dev, e->scan_snap, 0) != hipSuccess) {
     (void)hipGetLastError();
     gx_destroy(e);
     return GX_EIO;
   }
   e->scan_snap[0] = e->scan_snap[1] = ~0ull;
+  for (int i = 0; i < GX_QUIET_SLOTS; i++) e->scan_snap[2 + i] = 0;
   // per-host arrays hold this shard's Hl hosts; the message table also takes the packets received
   // from other shards (at most (H - Hl) * K), so it is sized H * K.
   size_t Hg = d.H, H = d.Hl, K = d.KE ? d.KE : 1;
@@ -1040,6 +1155,8 @@ int gx_create(const gx_params *p, gx_engine **out) {
   ALLOC(d.in_ovf, sizeof(uint4) * Hg * K);
   ALLOC(d.in_rec, sizeof(grec) * H * d.DR * p->packet_cap);
   ALLOC(d.work_cnt, sizeof(uint32_t) * GX_WC_N);
+  d.QW = 4 * nblk(H ? H : 1, 64);  // k_send's waves (launch_send: 64 hosts per 256-thread block)
+  ALLOC(d.quiet_w, sizeof(uint32_t) * 2 * d.QW);
   ALLOC(d.work, sizeof(uint32_t) * H);
   if (p->push_pull_mode == GX_PP_INITIATE) {
     ALLOC(e->pp_dev, sizeof(uint32_t) * 2 * Hg);
@@ -1169,6 +1286,7 @@ int gx_create(const gx_params *p, gx_engine **out) {
   HIPCHK(hipMemsetAsync(d.msg_len, 0, sizeof(uint32_t) * Hg * K, s));
   HIPCHK(hipMemsetAsync(e->in_cnt_buf, 0, sizeof(uint32_t) * 2 * H, s));
   HIPCHK(hipMemsetAsync(d.work_cnt, 0, sizeof(uint32_t) * GX_WC_N, s));
+  HIPCHK(hipMemsetAsync(d.quiet_w, 0, sizeof(uint32_t) * 2 * d.QW, s));  // (0: no round is quiet)
   HIPCHK(hipMemsetAsync(d.tick, 0, H, s));
   HIPCHK(hipMemsetAsync(d.ev_slot, 0xff, sizeof(int32_t) * H, s));  // -1: no listener
   k_fill_u16<<<256, 256, 0, s>>>(d.sbytes, d.R, (uint16_t)GX_STATIC_BYTES_DEFAULT);
@@ -1200,6 +1318,7 @@ int gx_set_round(gx_engine *e, int64_t round) {
     HIPCHK(hipMemsetAsync(e->d.work_cnt, 0, sizeof(uint32_t) * GX_WC_ERR, e->stream));
   }
   e->d.round = round;
+  quiet_invalidate(e);
   set_round_fields(e);
   int rc = wake_all(e);
   return rc ? rc : sync_check(e);
@@ -1220,6 +1339,7 @@ int gx_enable_timing(gx_engine *e, int on) {
 int gx_run_rounds(gx_engine *e, uint32_t n_rounds) {
   if (!e || e->d.G > 1 || e->d.round + n_rounds >= GX_MAX_ROUND) return GX_EINVAL;
   HIPCHK(hipSetDevice(e->device));
+  e->quiet_nowait = false;
   for (uint32_t i = 0; i < n_rounds; i++) {
     int rc = run_one_round(e);
     if (rc) return rc;
@@ -1270,6 +1390,7 @@ static void scan_one_view(gx_engine *e, uint32_t view, grec *list, uint32_t cap,
 static int api_add(gx_engine *e, const uint32_t *views, uint32_t fixed_view, const gx_service *svcs, uint32_t n,
                    int src, uint32_t *n_acc) {
   HIPCHK(hipSetDevice(e->device));
+  quiet_invalidate(e);
   if (views)
     for (uint32_t i = 0; i < n; i++)
       if (!own(e, views[i])) return GX_EINVAL;
@@ -1307,6 +1428,7 @@ int gx_merge_remote_state(gx_engine *e, uint32_t view, const gx_service *svcs, u
 int gx_merge(gx_engine *e, uint32_t dst, uint32_t src) {
   if (!e || !own(e, dst) || !own(e, src)) return GX_EINVAL;
   HIPCHK(hipSetDevice(e->device));
+  quiet_invalidate(e);
   set_round_fields(e);
   with_flags(vec_of(e), ev_of(e),
              [&](auto V, auto E) { k_merge_views<V(), E()><<<1, 256, 0, e->stream>>>(e->d, dst, src); });
@@ -1316,6 +1438,7 @@ int gx_merge(gx_engine *e, uint32_t dst, uint32_t src) {
 int gx_tombstone_others(gx_engine *e, uint32_t view, gx_service *out, uint32_t cap, uint32_t *n_out) {
   if (!e || !own(e, view) || (cap && !out)) return GX_EINVAL;
   HIPCHK(hipSetDevice(e->device));
+  quiet_invalidate(e);
   int rc = ensure_api(e, 256 + sizeof(grec) * (cap + 1));
   if (rc) return rc;
   uint32_t *dcnt = (uint32_t *)e->api_dev;
@@ -1344,6 +1467,7 @@ int gx_tombstone_services(gx_engine *e, uint32_t host, const uint16_t *running, 
     mask |= 1ull << running[i];
   }
   HIPCHK(hipSetDevice(e->device));
+  quiet_invalidate(e);
   int rc = ensure_api(e, 64);
   if (rc) return rc;
   set_round_fields(e);
@@ -1371,6 +1495,7 @@ int gx_tombstone_services(gx_engine *e, uint32_t host, const uint16_t *running, 
 int gx_expire_server(gx_engine *e, uint32_t view, uint32_t owner, int *expired) {
   if (!e || !own(e, view) || owner >= e->d.H) return GX_EINVAL;
   HIPCHK(hipSetDevice(e->device));
+  quiet_invalidate(e);
   int rc = ensure_api(e, 64);
   if (rc) return rc;
   set_round_fields(e);
@@ -1386,6 +1511,7 @@ int gx_notify_leave(gx_engine *e, uint32_t view, uint32_t node) { return gx_expi
 int gx_send_services(gx_engine *e, uint32_t host, const gx_service *svcs, uint32_t n, uint32_t n_passes) {
   if (!e || !own(e, host) || (n && !svcs) || n_passes < 1 || n_passes > GX_JOB_MAX_PASSES) return GX_EINVAL;
   HIPCHK(hipSetDevice(e->device));
+  quiet_invalidate(e);
   grec *drec;
   int rc = stage_recs(e, svcs, n, 0, &drec);
   if (rc) return rc;
@@ -1399,6 +1525,7 @@ int gx_broadcast_services(gx_engine *e, uint32_t host, const gx_service *list, u
   for (uint32_t i = 0; i < n; i++)
     if (list[i].host != host) return GX_EINVAL;
   HIPCHK(hipSetDevice(e->device));
+  quiet_invalidate(e);
   grec *drec;
   int rc = stage_recs(e, list, n, 0, &drec);
   if (rc) return rc;
@@ -1415,6 +1542,7 @@ int gx_broadcast_tombstones(gx_engine *e, uint32_t host, const gx_service *list,
     mask |= 1ull << list[i].svc;
   }
   HIPCHK(hipSetDevice(e->device));
+  quiet_invalidate(e);
   int rc = ensure_api(e, 256 + sizeof(grec) * (e->d.L + 1));
   if (rc) return rc;
   uint32_t *dcnt = (uint32_t *)e->api_dev;
@@ -1452,6 +1580,7 @@ int gx_is_new_service(gx_engine *e, uint32_t view, const gx_service *svc, int *o
 static int getb_impl(gx_engine *e, uint32_t host, uint32_t limit, uint32_t limit_bytes, uint32_t overhead,
                      gx_service *out, uint32_t *n_out) {
   HIPCHK(hipSetDevice(e->device));
+  quiet_invalidate(e);
   int rc = ensure_api(e, 256 + sizeof(grec) * (limit + 1));
   if (rc) return rc;
   uint32_t *dn = (uint32_t *)e->api_dev;
@@ -1489,6 +1618,7 @@ int gx_set_static_bytes(gx_engine *e, uint32_t owner_lo, uint32_t owner_hi, cons
   if (!e || owner_lo > owner_hi || owner_hi > e->d.H || (owner_hi > owner_lo && !bytes)) return GX_EINVAL;
   if (owner_hi == owner_lo) return GX_OK;
   HIPCHK(hipSetDevice(e->device));
+  quiet_invalidate(e);
   HIPCHK(hipStreamSynchronize(e->stream));
   size_t n = (size_t)(owner_hi - owner_lo) * e->d.S;
   HIPCHK(hipMemcpy(&e->d.sbytes[(size_t)owner_lo * e->d.S], bytes, sizeof(uint16_t) * n, hipMemcpyHostToDevice));
@@ -1716,6 +1846,7 @@ static int rebuild_logs(gx_engine *e) {
 int gx_add_listener(gx_engine *e, uint32_t view, uint32_t id, uint32_t capacity) {
   if (!e || !own(e, view) || capacity < 1 || capacity > GX_LISTENER_MAX_CAPACITY) return GX_EINVAL;
   HIPCHK(hipSetDevice(e->device));
+  quiet_invalidate(e);
   bool found = false;
   for (auto &l : e->listeners)
     if (l.view == view && l.id == id) {
@@ -1733,6 +1864,7 @@ int gx_add_listener(gx_engine *e, uint32_t view, uint32_t id, uint32_t capacity)
 int gx_remove_listener(gx_engine *e, uint32_t view, uint32_t id) {
   if (!e) return GX_EINVAL;
   HIPCHK(hipSetDevice(e->device));
+  quiet_invalidate(e);
   for (size_t i = 0; i < e->listeners.size(); i++)
     if (e->listeners[i].view == view && e->listeners[i].id == id) {
       e->listeners.erase(e->listeners.begin() + (long)i);
@@ -1799,6 +1931,7 @@ int gx_write_views(gx_engine *e, uint32_t lo, uint32_t hi, const uint64_t *in) {
   for (size_t i = 0; i < n; i++)
     if (st_of(in[i]) == 7 && in[i] != GX_SLOT_ABSENT) return GX_EINVAL;
   HIPCHK(hipSetDevice(e->device));
+  quiet_invalidate(e);
   HIPCHK(hipStreamSynchronize(e->stream));
   if (n) HIPCHK(hipMemcpy(&e->d.view[(size_t)(lo - e->d.lo) * e->d.R], in, sizeof(uint64_t) * n, hipMemcpyHostToDevice));
   set_round_fields(e);
@@ -1822,6 +1955,7 @@ int gx_write_slot(gx_engine *e, uint32_t view, const gx_service *svc) {
     r = g.r;
   }
   HIPCHK(hipSetDevice(e->device));
+  quiet_invalidate(e);
   set_round_fields(e);
   k_api_set_slot<<<1, 64, 0, e->stream>>>(e->d, view, r, w);
   return sync_check(e);
@@ -1935,6 +2069,7 @@ static bool ae_wave_blocks(const gx_engine *e) { return e->nblk <= XS_MAXB; }
 int gx_round_send(gx_engine *e) {
   if (!e) return GX_EINVAL;
   HIPCHK(hipSetDevice(e->device));
+  quiet_invalidate(e);
   int rc = round_send_impl(e);
   return rc ? rc : phase_done(e);
 }
@@ -2117,6 +2252,7 @@ int gx_inbox_unpack(gx_engine *e, const void *buf, uint64_t bytes) {
 int gx_round_merge(gx_engine *e) {
   if (!e) return GX_EINVAL;
   HIPCHK(hipSetDevice(e->device));
+  quiet_invalidate(e);
   int rc = round_merge_impl(e);
   return rc ? rc : phase_done(e);
 }
@@ -2408,9 +2544,10 @@ int gx_ae_merge_local(gx_engine *e) {
 int gx_ae_merge(gx_engine *e, const void *lead, uint64_t lead_bytes, const void *ret, uint64_t ret_bytes) {
   if (!e || (lead_bytes && !lead) || (ret_bytes && !ret)) return GX_EINVAL;
   HIPCHK(hipSetDevice(e->device));
+  quiet_invalidate(e);
   if (!ae_round(e)) return GX_OK;
   if (e->d.G < 2) {
-    int rc = ae_whole_impl(e);
+    int rc = ae_whole_impl(e, false);
     return rc ? rc : sync_check(e);
   }
   if (e->ae_planned_round != (int)e->d.round) return GX_EINVAL;
@@ -2505,6 +2642,7 @@ int gx_ae_skip_locked(gx_engine *e) {
 int gx_round_end(gx_engine *e) {
   if (!e || e->d.round + 1 >= GX_MAX_ROUND) return GX_EINVAL;  // rounds are 32-bit in jobs and sleepers
   HIPCHK(hipSetDevice(e->device));
+  quiet_invalidate(e);
   int rc = join_side(e);
   if (rc) return rc;
   e->d.round++;

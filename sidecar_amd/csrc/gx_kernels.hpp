@@ -1972,7 +1972,7 @@ GXD bool filt_used(const Dev &d, uint32_t pos) { return d.sfilt && pos != 0xffff
 // sleep > 0, senders' filter).
 template <int T, bool X, bool PLAN = false, bool FWD = false>
 GXD void send_host(const Dev &d, Acc &a, uint32_t idx, gx_job *pjs, int do_bt, unsigned &lost, PlanCall *pl,
-                   unsigned long long &kb, unsigned long long &kl, const TickFwd &fwd) {
+                   unsigned long long &kb, unsigned long long &kl, const TickFwd &fwd, uint32_t &quiet) {
   const uint32_t lane = threadIdx.x & (T - 1);
   {
     uint32_t u = d.lo + idx;
@@ -2012,6 +2012,7 @@ GXD void send_host(const Dev &d, Acc &a, uint32_t idx, gx_job *pjs, int do_bt, u
       send_planned<T>(d, a, idx, hs, pjs, pl, peers, np, kb, kl, (pre && fwd.pf0 == hs.fifo_head) ? fwd.npf : 0u);
       hs.lock = lock_snap(hs.lock, hs.flags, d.round + 1, d.p.lock_readers != 0);  // the lock for the next round
       if (lane == 0) *h = hs;
+      if (lane == 0 && d.p.lock_model) quiet = quiet_term(d, idx, hs);  // (planned sends only: the other paths fold 0)
     } else if (!X || !departed(d, u)) {
       const bool fd = X && d.p.fd_enable;
       uint32_t peers[16];
@@ -2137,8 +2138,21 @@ __global__ __launch_bounds__(256) void k_send(Dev d, int do_bt) {
   fwd.npf = 0;
   fwd.pf0 = 0;
   fwd.tick = 0;
-  if (d.snap && blockIdx.x == 0 && threadIdx.x == 0)  // scan_probe_begin: tagged with the round
-    *d.snap = ((uint64_t)(uint32_t)d.round << 32) | d.work_cnt[GX_WC_SCANS];
+  if (d.snap && blockIdx.x == 0) {  // (block-uniform) probe_begin: one 8-B store, tagged by the host
+    uint32_t v = 0xffffffffu;
+    if (d.snap_word == GX_SNAP_QUIET) {  // the last round's bound: the minimum of its waves' terms
+      __shared__ uint32_t s_q[4];
+      const uint32_t *q = d.quiet_w + (size_t)((d.round + 1) & 1) * d.QW;
+      for (uint32_t i = threadIdx.x; i < d.QW; i += 256) v = q[i] < v ? q[i] : v;
+      v = wave_min32(v);
+      if ((threadIdx.x & 63) == 0) s_q[threadIdx.x >> 6] = v;
+      __syncthreads();
+      for (int w = 0; w < 4; w++) v = s_q[w] < v ? s_q[w] : v;
+    } else {
+      v = d.work_cnt[d.snap_word];
+    }
+    if (threadIdx.x == 0) *d.snap = ((uint64_t)d.snap_tag << 32) | v;
+  }
   if constexpr (OWN > 0) {
     if (threadIdx.x == 0) {
       s_nscan = 0;
@@ -2170,12 +2184,20 @@ __global__ __launch_bounds__(256) void k_send(Dev d, int do_bt) {
     }
   }
   unsigned long long kb = 0, kl = 0;
+  // this host's quiet-round term (quiet_term; lead lanes of hosts): a host that sets none folds 0
+  uint32_t quiet = idx < d.Hl && (threadIdx.x & (T - 1)) == 0 ? 0u : 0xffffffffu;
   GX_KP(3);
   if (idx < d.Hl)  // (PLAN runs without departures: every host ticked)
     send_host<T, X, PLAN, PLAN && (OWN > 0)>(d, a, idx, s_pj[threadIdx.x / T], do_bt, lost,
-                                            s_pl[PLAN ? threadIdx.x / T : 0], kb, kl, fwd);
+                                            s_pl[PLAN ? threadIdx.x / T : 0], kb, kl, fwd, quiet);
   GX_KP(7);
   acc_flush(d, a);
+  if (d.p.lock_model) {  // the wave's term of the round's bound (Dev::quiet_w): a plain store per wave (2048
+    // atomicMin on one word cost 18 us per launch at cfg 5, 5 us when only waves that lower it issue one:
+    // the waves all finish together; profiles/quiet_rounds/)
+    quiet = wave_min32(quiet);
+    if ((threadIdx.x & 63) == 0) d.quiet_w[(size_t)(d.round & 1) * d.QW + blockIdx.x * 4u + (threadIdx.x >> 6)] = quiet;
+  }
   if (X && lost) ctr_atomic(d, C_LOST, lost);
   // algorithmic bytes: bookkeeping, FIFO jobs, records read (lists, ring), receiver slots read,
   // records and headers written (send_planned; the record-budget path counts the same per record)
