@@ -192,17 +192,17 @@ struct Dev {
   uint32_t *pexp;      // [Hl][PW] owners whose ExpireServer waits for the host's lock
   int in_round;        // a round phase is running: ExpireServer waits for the lock (ABI calls act directly)
   // gx.h lock_readers: push-pull merges of read-locked hosts waiting for their lock, in a pool of P
-  // rows (host v uses slot v % P, or dslot[v] below); each slot's host (GX_NOHOST = free), the
-  // pipeline places its merge holds and the lowest claimant of the current batch. ro_flag[t]: pair t of the last push-pull
-  // launch runs with a read-locked side (k_ae_ro takes it); ro_list: k_ae_ro's ordered list.
+  // rows; each slot's host (GX_NOHOST = free) and the pipeline places its merge holds. ro_flag[t]:
+  // pair t of the last push-pull launch runs with a read-locked side; ro_list, ro_n: those pairs in
+  // pair order (k_ae_claim writes them, k_ae_rox runs them).
   uint32_t P;
   uint64_t *dpool;     // [P][R]
-  uint32_t *dpool_host, *dpool_res, *dclaim;  // [P]
+  uint32_t *dpool_host, *dpool_res;  // [P]
   uint8_t *ro_flag;    // [H]
   uint32_t *ro_list;   // [H]
-  // lock_readers = 2 (the claimed pool): slots come from a free list, so host v's slot is dslot[v]
-  // (GX_NOHOST = no merge waits); claim_bits: the read-locked sides of the launch being claimed for,
-  // one bit per host (k_ae_claim sets and clears them); ro_n: the length of ro_list (k_ae_rox).
+  // Host v's slot is dslot[v] (GX_NOHOST = no merge waits) under either policy: k_ae_claim decides it,
+  // v % P or the next free slot. claim_bits: the read-locked sides of the launch being claimed for,
+  // one bit per host (k_ae_claim sets and clears them).
   uint32_t *dslot;       // [H]
   uint32_t *claim_bits;  // [ceil(H / 32)]
   uint32_t *ro_n;        // [1]
@@ -466,12 +466,14 @@ GXD bool ro_side(const Dev &d, uint32_t v) {
   return d.p.lock_readers && locked_in(d, lw) && !GX_LOCK_W_AT(lw, d.round) && GX_LOCK_BUF(lw) == 0u &&
          !(lw & (GX_LOCK_PENDING_EXPIRE | GX_LOCK_DEFER_MERGE)) && h->bt_next > d.round;
 }
-// a locked pair whose locked sides are all read-locked with no writer waiting: it runs (k_ae_ro)
+// a locked pair whose locked sides are all read-locked with no writer waiting: it runs (k_ae_rox)
 GXD bool ro_pair(const Dev &d, uint32_t a, uint32_t b) {
   return d.p.lock_readers && (!host_locked(d, a) || ro_side(d, a)) && (!host_locked(d, b) || ro_side(d, b));
 }
 // the inbound pipeline's room for gossip records of local host vi with lock word lw: a waiting merge
-// holds min(n, 26) of its places (gx.h GX_LOCK_DEFER_RES). Oracle: pipe_cap.
+// holds min(n, 26) of its places (gx.h GX_LOCK_DEFER_RES). Oracle: pipe_cap. (The direct-mapped
+// slot v % P is dslot[v] as well; it stays arithmetic here because this is inlined into k_send,
+// k_merge_seg, k_lock_append and k_fd_recv, whose device code is kept as it was measured.)
 GXD uint32_t pipe_cap(const Dev &d, uint32_t vi, uint32_t lw) {
   if (!(lw & GX_LOCK_DEFER_MERGE)) return d.C;
   uint32_t slot = (d.lo + vi) % d.P;

@@ -701,19 +701,15 @@ static bool ae_partner(const Dev &d, uint32_t i, uint32_t *out) {
   *out = base + (idx >= self ? idx + 1 : idx);
   return true;
 }
-// gx.h lock_readers: the read-locked exchanges of the last push-pull launch (k_ae_ro; with the
-// claimed pool k_ae_claim and k_ae_rox over at most as many blocks as the launch itself had)
+// gx.h lock_readers: the read-locked exchanges of the last push-pull launch: k_ae_claim gives their
+// read-locked sides pool slots by the policy's rule, then k_ae_rox runs the pairs in parallel over
+// at most as many blocks as the launch itself had
 static void ae_ro_launch(gx_engine *e, const uint32_t *pa, const uint32_t *pb, uint64_t key0, uint64_t key1, uint32_t np) {
   const Dev &d = e->d;
-  if (d.p.lock_readers == GX_LOCK_READERS_CLAIMED) {  // slots from the free list, then the pairs in parallel
-    k_ae_claim<<<1, 256, 0, e->stream>>>(d, pa, pb, key0, key1, np);
-    with_flags(vec_of(e), ev_of(e), [&](auto V, auto E) {
-      k_ae_rox<V(), E()><<<ae_grid(np, 1), 256, 0, e->stream>>>(d, pa, pb, key0, key1);
-    });
-    return;
-  }
-  with_flags(vec_of(e), ev_of(e),
-             [&](auto V, auto E) { k_ae_ro<V(), E()><<<1, 256, 0, e->stream>>>(d, pa, pb, key0, key1, np); });
+  k_ae_claim<<<1, 256, 0, e->stream>>>(d, pa, pb, key0, key1, np);
+  with_flags(vec_of(e), ev_of(e), [&](auto V, auto E) {
+    k_ae_rox<V(), E()><<<ae_grid(np, 1), 256, 0, e->stream>>>(d, pa, pb, key0, key1);
+  });
 }
 // The planned pairs' exchange: the ChangeEvent variant while some view has a listener, else two
 // tiles in flight where the caller asks (pf2), else one.
@@ -993,7 +989,7 @@ int gx_destroy(gx_engine *e) {
                   e->ae_pcount, d.view, d.minexp, d.own_status, d.hs, d.fifo, d.sleep, d.dq, d.arena, d.arena_len, d.msg, d.msg_w0, d.msg_len,
                   d.msg_dst, e->in_cnt_buf, d.scan_list, d.scan_cnt, d.tick,
                   d.sbytes, d.srvt, d.vlc, d.ev_slot, d.ev_log, d.ev_cnt, d.ctr, d.in_hdr, d.in_ovf, d.in_rec, d.work_cnt, d.quiet_w, d.work, d.mrec, e->pp_dev, e->pp_prow, e->name_rank, e->api_dev, e->conv_bad, e->digest_buf, d.kprof,
-                  d.mem, d.fd_dl, d.fdh, d.fdm, d.fd_len, d.fd_peers, d.fd_np, d.fd_snap, d.lkb, d.pexp, d.dpool, d.dpool_host, d.dpool_res, d.dclaim, d.ro_flag, d.ro_list, d.dslot, d.claim_bits, d.ro_n, d.fdq};
+                  d.mem, d.fd_dl, d.fdh, d.fdm, d.fd_len, d.fd_peers, d.fd_np, d.fd_snap, d.lkb, d.pexp, d.dpool, d.dpool_host, d.dpool_res, d.ro_flag, d.ro_list, d.dslot, d.claim_bits, d.ro_n, d.fdq};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   codec_free(e);
@@ -1206,21 +1202,17 @@ int gx_create(const gx_params *p, gx_engine **out) {
       ALLOC(d.dpool, sizeof(uint64_t) * d.P * d.R);
       ALLOC(d.dpool_host, sizeof(uint32_t) * d.P);
       ALLOC(d.dpool_res, sizeof(uint32_t) * d.P);
-      ALLOC(d.dclaim, sizeof(uint32_t) * d.P);
       ALLOC(d.ro_flag, H);
       ALLOC(d.ro_list, sizeof(uint32_t) * H);
+      ALLOC(d.ro_n, sizeof(uint32_t));
+      ALLOC(d.dslot, sizeof(uint32_t) * Hg);  // each host's slot, the claimants' bits
+      ALLOC(d.claim_bits, sizeof(uint32_t) * ((Hg + 31) / 32));
       HIPCHK(hipMemset(d.dpool_host, 0xff, sizeof(uint32_t) * d.P));
-      HIPCHK(hipMemset(d.dclaim, 0xff, sizeof(uint32_t) * d.P));
       HIPCHK(hipMemset(d.dpool_res, 0, sizeof(uint32_t) * d.P));
       HIPCHK(hipMemset(d.ro_flag, 0, H));
-      if (p->lock_readers == GX_LOCK_READERS_CLAIMED) {  // slots from a free list: each host's slot, the claimants' bits
-        ALLOC(d.dslot, sizeof(uint32_t) * Hg);
-        ALLOC(d.claim_bits, sizeof(uint32_t) * ((Hg + 31) / 32));
-        ALLOC(d.ro_n, sizeof(uint32_t));
-        HIPCHK(hipMemset(d.dslot, 0xff, sizeof(uint32_t) * Hg));
-        HIPCHK(hipMemset(d.claim_bits, 0, sizeof(uint32_t) * ((Hg + 31) / 32)));
-        HIPCHK(hipMemset(d.ro_n, 0, sizeof(uint32_t)));
-      }
+      HIPCHK(hipMemset(d.ro_n, 0, sizeof(uint32_t)));
+      HIPCHK(hipMemset(d.dslot, 0xff, sizeof(uint32_t) * Hg));
+      HIPCHK(hipMemset(d.claim_bits, 0, sizeof(uint32_t) * ((Hg + 31) / 32)));
     }
     if (p->fd_handoff_shared) {  // the handoff queue's places after the 53 the handler's chain holds
       d.HQ = d.C > GX_LOCK_HANDLER_AT ? d.C - GX_LOCK_HANDLER_AT : 0;

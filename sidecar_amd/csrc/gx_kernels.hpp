@@ -3696,7 +3696,7 @@ GXD void ae_pair(const Dev &d, uint32_t a, uint32_t b, bool both, unsigned long 
 // side's LocalState blocks behind the pending writer, so the exchange does not run (returns true:
 // skip it); with lock_model = 0 it runs and `locked` says its merges are counted. Block-uniform.
 // gx.h lock_readers: a pair whose locked sides are all read-locked with no writer waiting is flagged
-// (ro_flag[t], t its index in the launch) for k_ae_ro, which runs it after the launch.
+// (ro_flag[t], t its index in the launch) for k_ae_claim and k_ae_rox, which run it after the launch.
 GXD bool ae_lock_skip(const Dev &d, uint32_t a, uint32_t b, bool &locked, uint32_t t) {
   locked = host_locked(d, a) || host_locked(d, b);
   if (!locked) return false;
@@ -3726,6 +3726,16 @@ GXD void ae_pair_hosts(const Dev &d, uint32_t t, uint64_t key0, uint64_t key1, u
   a = base + feistel_perm(key, 2 * q, m);
   b = base + feistel_perm(key, 2 * q + 1, m);
 }
+// Pair t of a push-pull launch: of the initiate batch pa/pb, or (pa null) of the round's matching.
+GXD void ae_launch_hosts(const Dev &d, const uint32_t *pa, const uint32_t *pb, uint32_t t, uint64_t key0,
+                         uint64_t key1, uint32_t &a, uint32_t &b) {
+  if (pa) {
+    a = pa[t];
+    b = pb[t];
+  } else {
+    ae_pair_hosts(d, t, key0, key1, a, b);
+  }
+}
 // A block takes a chunk of up to 256 pairs (np / gridDim.x rounded up): each thread checks one
 // pair's members (a crashed member, the failure detector's view, the ServicesState lock) so the
 // chunk's skipped pairs cost one round trip together, then the block merges the pairs that run,
@@ -3735,6 +3745,8 @@ template <bool VEC, bool EV, int PF, bool NT, bool NTS = false>
 GXD void ae_round_pair(const Dev &d, uint64_t key0, uint64_t key1) {
   __shared__ unsigned long long s_wave[4];
   __shared__ unsigned long long s_red[4];
+  // ae_pair_hosts and the members' test below are spelled out here and in ae_round_pairs: calling
+  // shared helpers changed the device code of k_ae, k_ae_ev and one k_ae_chunk, which is kept as measured
   uint32_t t = blockIdx.x, base = 0, m = d.H, q = t;
   uint64_t key = key0;
   if (d.pair_split) {
@@ -3790,7 +3802,7 @@ GXD void ae_round_pairs(const Dev &d, uint64_t key0, uint64_t key1, uint32_t np)
     }
     if (ok) {
       const bool locked = host_locked(d, a) || host_locked(d, b);
-      const bool ro = locked && d.p.lock_model && ro_pair(d, a, b);  // k_ae_ro runs it (lock_readers)
+      const bool ro = locked && d.p.lock_model && ro_pair(d, a, b);  // k_ae_rox runs it (lock_readers)
       if (ro) {
         d.ro_flag[tq] = 1;
         atomicMin(&d.ctr->first_drop[shard_id()][1], (unsigned long long)d.round);
@@ -3848,117 +3860,28 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
 
 // gx.h lock_readers: the exchanges of the last push-pull launch whose locked sides are all
 // read-locked with no writer waiting (ro_flag[t]; pair t of the matching round from key0/key1, or
-// of the initiate batch pa/pb). One block, after the launch: (1) the read-locked sides claim their
-// pool slots (slot v % P, free at the launch's start: the lowest host id gets it, whatever the
-// order, as the oracle's ae_claims); (2) the flagged pairs in pair order: a read-locked side keeps
-// the partner's pre-exchange row in its slot (services_delegate.go:153-167 -> services_state.go:
-// 367-373 -> UpdateService :138-140, blocked behind the lock) or counts it lost, then the unlocked
-// side merges the partner's row (ae_pair, one direction); (3) the claims are reset. The pairs are
-// disjoint and no other pair of the launch touches their rows, so running them after the launch is
-// the oracle's result (ae_exchange_read_locked). Clears ro_flag.
-template <bool VEC, bool EV>
-__global__ __launch_bounds__(256) void k_ae_ro(Dev d, const uint32_t *pa, const uint32_t *pb, uint64_t key0, uint64_t key1,
-                                               uint32_t n) {
-  __shared__ unsigned long long s_wave[4];
-  __shared__ unsigned long long s_red[4];
-  __shared__ uint32_t s_pre[256];
-  __shared__ uint32_t s_n;
-  const uint32_t tid = threadIdx.x, per = (n + 255) / 256, t0 = tid * per < n ? tid * per : n;
-  const uint32_t t1 = t0 + per < n ? t0 + per : n;
-  auto hosts = [&](uint32_t t, uint32_t &a, uint32_t &b) {
-    if (pa) {
-      a = pa[t];
-      b = pb[t];
-    } else {
-      ae_pair_hosts(d, t, key0, key1, a, b);
-    }
-  };
-  uint32_t c = 0;
-  for (uint32_t t = t0; t < t1; t++) {  // (1) claims
-    if (!d.ro_flag[t]) continue;
-    c++;
-    uint32_t a, b;
-    hosts(t, a, b);
-    for (int k = 0; k < 2; k++) {
-      const uint32_t x = k ? b : a;
-      if (!host_locked(d, x)) continue;
-      const uint32_t slot = x % d.P;
-      if (d.dpool_host[slot] == GX_NOHOST) atomicMin(&d.dclaim[slot], x);
-    }
-  }
-  s_pre[tid] = c;
-  __syncthreads();
-  if (tid == 0) {  // the flagged pairs' places in pair order (threads hold consecutive ranges)
-    uint32_t run = 0;
-    for (uint32_t i = 0; i < 256; i++) {
-      const uint32_t x = s_pre[i];
-      s_pre[i] = run;
-      run += x;
-    }
-    s_n = run;
-  }
-  __syncthreads();
-  uint32_t pos = s_pre[tid];
-  for (uint32_t t = t0; t < t1; t++)
-    if (d.ro_flag[t]) {
-      d.ro_list[pos++] = t;
-      d.ro_flag[t] = 0;
-    }
-  __threadfence();
-  __syncthreads();
-  const uint32_t nro = s_n;
-  for (uint32_t k = 0; k < nro; k++) {  // (2) the exchanges
-    uint32_t a, b;
-    hosts(d.ro_list[k], a, b);
-    const bool la = host_locked(d, a), lb = host_locked(d, b);
-    __syncthreads();  // every thread has read the lock words before a side's DEFER bit is set
-    for (int q = 0; q < 2; q++) {  // a read-locked side keeps the partner's row (before any merge)
-      const uint32_t x = q ? b : a, y = q ? a : b;
-      if (!(q ? lb : la)) continue;
-      const uint32_t slot = x % d.P;
-      if (d.dclaim[slot] != x) {  // the slot went to another host: the merge is lost
-        if (tid == 0) ctr_atomic(d, C_AE_DEFER_LOST, 1);
-        continue;
-      }
-      const uint64_t *src = vrow(d, y);
-      uint64_t *dst = &d.dpool[(size_t)slot * d.R];
-      unsigned long long np = 0;
-      for (uint32_t r = tid; r < d.R; r += blockDim.x) {
-        const uint64_t w = src[r];
-        dst[r] = w;
-        np += st_of(w) != GX_ABSENT;
-      }
-      np = block_sum(np, s_red);
-      if (tid == 0) {
-        d.dpool_host[slot] = x;
-        d.dpool_res[slot] = np < GX_LOCK_DEFER_RES ? (uint32_t)np : GX_LOCK_DEFER_RES;
-        hst(d, x)->lock |= GX_LOCK_DEFER_MERGE;
-        ctr_atomic(d, C_AE_DEFER, 1);
-        kbytes(d, GX_K_AE, 16ull * d.R, 0);
-      }
-    }
-    __threadfence();
-    __syncthreads();
-    if (!la) ae_pair<VEC, 1, false, EV>(d, a, b, false, s_wave, s_red);  // the unlocked side merges now
-    else if (!lb) ae_pair<VEC, 1, false, EV>(d, b, a, false, s_wave, s_red);
-    if (tid == 0) ctr_atomic(d, C_AEX, 1);
-    __syncthreads();
-  }
-  for (uint32_t x = tid; x < d.P; x += blockDim.x) d.dclaim[x] = GX_NOHOST;  // (3)
-}
-// gx.h lock_readers = 2, the claimed pool: k_ae_ro's work in two launches. k_ae_claim (one block,
-// after the push-pull launch and its membership half) hands out the pool's slots: the claimants are
-// the read-locked sides of the flagged pairs, the free slots those free now (no slot is freed before
-// the next round's drain); in ascending host id the k-th claimant takes the k-th free slot in
-// ascending slot index (dslot[x], dpool_host[slot]), and a claimant past the last free slot is lost
-// (its dslot stays GX_NOHOST). With one slot this is k_ae_ro's rule, the lowest host id gets it.
-// It also writes the flagged pairs in pair order (ro_list, *ro_n) for k_ae_rox and clears ro_flag.
-// Three ordered block scans: the pairs per thread range, the free slots, the claimants' bitmap.
+// of the initiate batch pa/pb) run in two launches after it and its membership half: a read-locked
+// side keeps the partner's pre-exchange row in a pool slot (services_delegate.go:153-167 ->
+// services_state.go:367-373 -> UpdateService :138-140, blocked behind the lock) or loses it, then the
+// unlocked side merges the partner's row (ae_pair, one direction). The pairs are disjoint and no
+// other pair of the launch touches their rows, so running them after the launch is the oracle's
+// result (ae_exchange_read_locked).
+// k_ae_claim (one block) hands out the pool's slots: the claimants are the read-locked sides of the
+// flagged pairs, the free slots those free now (no slot is freed before the next round's drain). An
+// admitted claimant x gets dslot[x] and dpool_host[slot]; every other one is lost, counted here, and
+// its dslot stays GX_NOHOST. The two policies differ in the slot a claimant gets:
+//  - lock_readers = 1, direct-mapped: x wants slot x % P and gets it if it is free and x is the lowest
+//    claimant that wants it, whatever the order (the oracle's ae_claims);
+//  - lock_readers = 2, claimed: in ascending host id the k-th claimant takes the k-th free slot in
+//    ascending slot index, and the claimants past the last free slot are lost.
+// With one slot both give it to the lowest host id. The kernel also writes the flagged pairs in pair
+// order (ro_list, *ro_n) for k_ae_rox and clears ro_flag. Ordered block scans: the pairs per thread
+// range and, for the claimed pool, the free slots and the claimants' bitmap.
 #define GX_POOL_MAX 4096  // gx.h lock_defer_slots' bound (gx_create checks it)
 __global__ __launch_bounds__(256) void k_ae_claim(Dev d, const uint32_t *pa, const uint32_t *pb, uint64_t key0,
                                                   uint64_t key1, uint32_t n) {
   __shared__ unsigned long long s_wave[4];
-  __shared__ uint16_t s_free[GX_POOL_MAX];
+  __shared__ uint32_t s_slot[GX_POOL_MAX];  // claimed: the free slots; direct-mapped: each slot's lowest claimant
   const uint32_t tid = threadIdx.x, per = (n + 255) / 256, t0 = tid * per < n ? tid * per : n;
   const uint32_t t1 = t0 + per < n ? t0 + per : n;
   uint32_t c = 0;
@@ -3970,27 +3893,45 @@ __global__ __launch_bounds__(256) void k_ae_claim(Dev d, const uint32_t *pa, con
     d.ro_list[pos++] = t;
     d.ro_flag[t] = 0;
     uint32_t a, b;
-    if (pa) {
-      a = pa[t];
-      b = pb[t];
-    } else {
-      ae_pair_hosts(d, t, key0, key1, a, b);
-    }
+    ae_launch_hosts(d, pa, pb, t, key0, key1, a, b);
     if (host_locked(d, a)) atomicOr(&d.claim_bits[a >> 5], 1u << (a & 31));
     if (host_locked(d, b)) atomicOr(&d.claim_bits[b >> 5], 1u << (b & 31));
   }
   if (tid == 0) *d.ro_n = (uint32_t)tot;
   if (!tot) return;  // block-uniform: no flagged pair, no bit set
+  const uint32_t nw = (d.H + 31) / 32;
+  if (d.p.lock_readers != GX_LOCK_READERS_CLAIMED) {  // direct-mapped (block-uniform)
+    for (uint32_t s = tid; s < d.P; s += 256) s_slot[s] = GX_NOHOST;
+    __syncthreads();  // s_slot; and every claimant's bit is set (the atomics are done at the barrier)
+    for (uint32_t w = tid; w < nw; w += 256)  // the lowest claimant of each free slot
+      for (uint32_t bits = atomicOr(&d.claim_bits[w], 0u); bits; bits &= bits - 1u) {  // read at the L2
+        const uint32_t x = 32u * w + (uint32_t)__ffs(bits) - 1u, slot = x % d.P;
+        if (d.dpool_host[slot] == GX_NOHOST) atomicMin(&s_slot[slot], x);
+      }
+    __syncthreads();  // no slot's host is written before every claim has read it
+    uint32_t lost = 0;
+    for (uint32_t w = tid; w < nw; w += 256)
+      for (uint32_t bits = atomicExch(&d.claim_bits[w], 0u); bits; bits &= bits - 1u) {  // and cleared
+        const uint32_t x = 32u * w + (uint32_t)__ffs(bits) - 1u, slot = x % d.P;
+        if (s_slot[slot] == x) {
+          d.dslot[x] = slot;
+          d.dpool_host[slot] = x;
+        } else {
+          lost++;  // the slot is taken or went to a lower host
+        }
+      }
+    block_ctr(d, C_AE_DEFER_LOST, lost, s_wave);
+    return;
+  }
   uint32_t nfree = 0;
   for (uint32_t s0 = 0; s0 < d.P; s0 += 256) {  // the free slots, ascending
     const uint32_t s = s0 + tid;
     const bool f = s < d.P && d.dpool_host[s] == GX_NOHOST;
     const uint32_t at = nfree + (uint32_t)block_excl_scan64(f, s_wave, tot);
-    if (f) s_free[at] = (uint16_t)s;
+    if (f) s_slot[at] = s;
     nfree += (uint32_t)tot;
   }
-  __syncthreads();  // s_free; and every claimant's bit is set (the atomics are done at the barrier)
-  const uint32_t nw = (d.H + 31) / 32;
+  __syncthreads();  // s_slot; and every claimant's bit is set (the atomics are done at the barrier)
   uint32_t base = 0;
   for (uint32_t w0 = 0; w0 < nw; w0 += 256) {  // the claimants, ascending: rank = set bits below
     const uint32_t w = w0 + tid;
@@ -3998,7 +3939,7 @@ __global__ __launch_bounds__(256) void k_ae_claim(Dev d, const uint32_t *pa, con
     uint32_t k = base + (uint32_t)block_excl_scan64((unsigned long long)__popc(bits), s_wave, tot);
     for (; bits; bits &= bits - 1u, k++) {
       if (k >= nfree) break;  // lost, with every higher claimant
-      const uint32_t x = 32u * w + (uint32_t)__ffs(bits) - 1u, slot = s_free[k];
+      const uint32_t x = 32u * w + (uint32_t)__ffs(bits) - 1u, slot = s_slot[k];
       d.dslot[x] = slot;
       d.dpool_host[slot] = x;
     }
@@ -4010,7 +3951,7 @@ __global__ __launch_bounds__(256) void k_ae_claim(Dev d, const uint32_t *pa, con
 // no slot serves two hosts): a read-locked side with a slot keeps the partner's pre-exchange row there
 // (16-B loads and stores on even rows) before any merge of the pair and holds min(n, 26) pipeline
 // places, one without a slot lost its merge (k_ae_claim counted it); then the unlocked side merges
-// the partner's row, as in k_ae_ro.
+// the partner's row.
 template <bool VEC, bool EV>
 __global__ __launch_bounds__(256) void k_ae_rox(Dev d, const uint32_t *pa, const uint32_t *pb, uint64_t key0,
                                                 uint64_t key1) {
@@ -4018,14 +3959,8 @@ __global__ __launch_bounds__(256) void k_ae_rox(Dev d, const uint32_t *pa, const
   __shared__ unsigned long long s_red[4];
   const uint32_t tid = threadIdx.x, nro = *d.ro_n;
   for (uint32_t k = blockIdx.x; k < nro; k += gridDim.x) {  // block-uniform
-    const uint32_t t = d.ro_list[k];
     uint32_t a, b;
-    if (pa) {
-      a = pa[t];
-      b = pb[t];
-    } else {
-      ae_pair_hosts(d, t, key0, key1, a, b);
-    }
+    ae_launch_hosts(d, pa, pb, d.ro_list[k], key0, key1, a, b);
     const bool la = host_locked(d, a), lb = host_locked(d, b);
     __syncthreads();  // every thread has read the lock words before a side's DEFER bit is set
     for (int q = 0; q < 2; q++) {
@@ -4084,7 +4019,7 @@ __global__ __launch_bounds__(256) void k_defer_drain(Dev d) {
   if (threadIdx.x == 0) {
     d.dpool_host[s] = GX_NOHOST;
     d.dpool_res[s] = 0;
-    if (d.dslot) d.dslot[x] = GX_NOHOST;  // the claimed pool (lock_readers = 2)
+    d.dslot[x] = GX_NOHOST;
     d.hs[vi].lock = lw & ~GX_LOCK_DEFER_MERGE;
     d.tick[vi] = 2;
   }

@@ -1,7 +1,9 @@
 """The claimed pool of waiting push-pull merges (gx.h lock_readers = 2: k_ae_claim, k_ae_rox,
 k_defer_drain) on the HIP engine. The oracle has no claimed pool; a pool that loses nothing must
 match the oracle's direct-mapped pool with a slot per host (lock_defer_slots = n_hosts: v % P = v)
-bit for bit, and with one slot the two policies coincide, losses included. The schedules and pool
+bit for bit, and with one slot the two policies coincide, losses included. The direct-mapped pool
+(lock_readers = 1, the same kernels with the slot rule v % P) runs beside the oracle's at the sizes
+where it loses merges. The schedules and pool
 sizes are tests/lock_pool_cases.py's; tests/test_lock_pool_cpu.py pins that every pool has room."""
 import pytest
 
@@ -30,11 +32,18 @@ def test_claimed_pool_lossless_parity(oracle_lib, gx_lib, name):
 
 
 @pytest.mark.parametrize("name", CONTRAST)
-def test_direct_mapped_loses_where_claimed_does_not(gx_lib, name):
+def test_direct_mapped_loses_where_claimed_does_not(oracle_lib, gx_lib, name):
+    """The direct-mapped engine beside the oracle's direct-mapped pool of the same size, where many
+    claimants want one slot and slots stay taken across rounds (the oracle's ae_claims)."""
     kw, slots = schedule(name)
-    m = Engine(default_params(gx_lib, lock_readers=LOCK_READERS_MAPPED, lock_defer_slots=slots, **kw), lib=gx_lib)
+    mapped = dict(lock_readers=LOCK_READERS_MAPPED, lock_defer_slots=slots, **kw)
+    m = Engine(default_params(gx_lib, **mapped), lib=gx_lib)
+    o = Engine(default_params(oracle_lib, **mapped), lib=oracle_lib)
     c = _claimed(gx_lib, kw, slots)
-    m.run_rounds(ROUNDS)
+    for chunk in CHUNKS:
+        m.run_rounds(chunk)
+        o.run_rounds(chunk)
+        assert_same(m, o, f"{name} direct-mapped round {m.round}")
     c.run_rounds(ROUNDS)
     print(f"{name}: direct-mapped lost {m.stats()['ae_defer_lost']} of {m.stats()['ae_deferred']} deferred, "
           f"claimed lost {c.stats()['ae_defer_lost']} of {c.stats()['ae_deferred']}")

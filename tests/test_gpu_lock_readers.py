@@ -1,4 +1,4 @@
-"""Push-pull exchanges with a read-locked side (gx.h lock_readers, k_ae_ro / k_defer_drain) on the
+"""Push-pull exchanges with a read-locked side (gx.h lock_readers, k_ae_claim / k_ae_rox / k_defer_drain) on the
 HIP engine against the oracle, bit for bit: views, host states (lock words with the write-lock and
 waiting-merge bits), queue digests, server times and every counter (ae_deferred and ae_defer_lost
 included). Go's sync.RWMutex admits LocalState's RLock (services_delegate.go:148) while only
