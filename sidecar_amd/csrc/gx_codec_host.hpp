@@ -6,28 +6,7 @@
 #include <algorithm>
 #include <string>
 
-// grow-only device buffer
-struct DevBuf {
-  void *p = nullptr;
-  size_t cap = 0;
-};
-static int dbuf(DevBuf &b, size_t bytes, void **out) {
-  if (bytes > b.cap) {
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.cap = 0;
-    size_t c = 1 << 16;
-    while (c < bytes) c <<= 1;
-    if (hipMalloc(&b.p, c) != hipSuccess) {
-      (void)hipGetLastError();
-      return GX_ENOMEM;
-    }
-    b.cap = c;
-  }
-  *out = b.p;
-  return GX_OK;
-}
-// bump allocator over one grow-only buffer (all pieces of one phase of a call)
+// bump allocator over one grow-only buffer (DevBuf; all pieces of one phase of a call)
 struct Bump {
   size_t off = 0;
   template <class T>
@@ -75,7 +54,7 @@ static int d2h_staged(gx_engine *e, Pinned &pn, char *dst, const char *src, size
 struct CodecState {
   Pinned pin2;                   // staging for LocalState copies to the caller
   gxc::Names nm;                 // device pointers
-  std::vector<void *> owned;     // device allocations of the names tables
+  DevMem owned;                  // the names tables and `seen`
   std::vector<uint32_t> ehost_len;
   uint32_t *seen = nullptr;      // [R] duplicate record keys
   DevBuf out;                    // encoder output
@@ -86,15 +65,11 @@ struct CodecState {
 static void codec_free(gx_engine *e) {
   CodecState *c = e->codec;
   if (!c) return;
-  for (void *p : c->owned) (void)hipFree(p);
-  if (c->seen) (void)hipFree(c->seen);
-  for (DevBuf *b : {&c->out, &c->enc, &c->in, &c->ph1, &c->ph2, &c->ph3})
-    if (b->p) (void)hipFree(b->p);
   for (int i = 0; i < 2; i++) {
     if (c->pin2.p[i]) (void)hipHostFree(c->pin2.p[i]);
     if (c->pin2.ev[i]) (void)hipEventDestroy(c->pin2.ev[i]);
   }
-  delete c;
+  delete c;  // with its device memory (DevMem, DevBuf)
   e->codec = nullptr;
 }
 
@@ -141,15 +116,10 @@ static uint64_t fnv1a(const char *s, size_t n) {
 }
 template <class T>
 static int upload(gx_engine *e, const T *src, size_t n, const T **dst) {
-  void *p = nullptr;
-  size_t bytes = std::max<size_t>(sizeof(T) * n, 16);
-  if (hipMalloc(&p, bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    return GX_ENOMEM;
-  }
-  e->codec->owned.push_back(p);
+  T *p;
+  GXTRY(e->codec->owned.take(p, std::max<size_t>(sizeof(T) * n, 16)));
   if (n) HIPCHK(hipMemcpy(p, src, sizeof(T) * n, hipMemcpyHostToDevice));
-  *dst = (const T *)p;
+  *dst = p;
   return GX_OK;
 }
 
@@ -492,12 +462,11 @@ int gx_set_names(gx_engine *e, const gx_names *in) {
   nm.id_mask = isz - 1;
   nm.ecluster_len = (uint32_t)ec.size();
   c->ehost_len = ehl;
-  if (hipMalloc((void **)&c->seen, sizeof(uint32_t) * R) != hipSuccess) {
-    (void)hipGetLastError();
+  rc = c->owned.take(c->seen, sizeof(uint32_t) * R, 0, e->stream);
+  if (rc) {
     codec_free(e);
-    return GX_ENOMEM;
+    return rc;
   }
-  HIPCHK(hipMemset(c->seen, 0, sizeof(uint32_t) * R));
   // every record's static message bytes follow the names (packPacket lengths = codec lengths)
   std::vector<uint16_t> sb(R);
   for (uint32_t r = 0; r < R; r++)

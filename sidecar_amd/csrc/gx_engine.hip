@@ -45,6 +45,12 @@
       return GX_EIO;                                                                       \
     }                                                                                      \
   } while (0)
+// a step's GX_* result: anything but GX_OK is returned at once
+#define GXTRY(x)         \
+  do {                   \
+    int rc_ = (x);       \
+    if (rc_) return rc_; \
+  } while (0)
 
 static uint32_t pow2_at_least(uint32_t x) {
   uint32_t v = 1;
@@ -62,13 +68,80 @@ struct TimedLaunch {
   hipEvent_t a, b;
 };
 
+// Device allocations that share one lifetime (an engine's, the codec's name tables, one call's
+// temporaries): every take() is freed by release(), at the latest when the owner goes.
+struct DevMem {
+  std::vector<void *> ptrs;
+  DevMem() = default;
+  DevMem(const DevMem &) = delete;
+  DevMem &operator=(const DevMem &) = delete;
+  ~DevMem() { release(); }
+  template <class T>
+  int take(T *&p, size_t bytes) {
+    void *q = nullptr;
+    if (hipMalloc(&q, bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      return GX_ENOMEM;
+    }
+    ptrs.push_back(q);
+    p = (T *)q;
+    return GX_OK;
+  }
+  // ... with every byte set to `fill` on stream s, so before whatever s runs next (a hipMemset on the
+  // null stream is ordered with neither the host nor a non-blocking stream)
+  template <class T>
+  int take(T *&p, size_t bytes, int fill, hipStream_t s) {
+    GXTRY(take(p, bytes));
+    if (bytes) HIPCHK(hipMemsetAsync(p, fill, bytes, s));
+    return GX_OK;
+  }
+  // one buffer (or none: p == nullptr) ahead of the rest
+  template <class T>
+  void drop(T *&p) {
+    ptrs.erase(std::remove(ptrs.begin(), ptrs.end(), (void *)p), ptrs.end());
+    (void)hipFree(p);
+    p = nullptr;
+  }
+  void release() {
+    for (void *q : ptrs) (void)hipFree(q);
+    ptrs.clear();
+  }
+};
+
+// grow-only device buffer (a power of two >= min_cap bytes)
+struct DevBuf {
+  void *p = nullptr;
+  size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf &) = delete;
+  DevBuf &operator=(const DevBuf &) = delete;
+  ~DevBuf() { (void)hipFree(p); }
+};
+static int dbuf(DevBuf &b, size_t bytes, void **out, size_t min_cap = 1 << 16) {
+  if (bytes > b.cap) {
+    (void)hipFree(b.p);
+    b.p = nullptr;
+    b.cap = 0;
+    size_t c = min_cap;
+    while (c < bytes) c <<= 1;
+    if (hipMalloc(&b.p, c) != hipSuccess) {
+      (void)hipGetLastError();
+      return GX_ENOMEM;
+    }
+    b.cap = c;
+  }
+  *out = b.p;
+  return GX_OK;
+}
+
 // Quiet-round bounds asked for and not stored yet, one every second round: with all of them
 // outstanding the host is 8 rounds ahead of the device and lets it catch up (quiet_probe). 8 rounds
 // are 250 us of queued work at cfg 5; the shortest quiet stretches of the test schedules are 10.
 #define GX_QUIET_SLOTS 4
 
 struct gx_engine {
-  Dev d;
+  Dev d{};
+  DevMem mem;  // every device buffer that lives as long as the engine
   hipStream_t stream;      // where all device work goes (own_stream, or the caller's: gx_set_stream)
   hipStream_t own_stream;
   // shard-local push-pull pairs run on side_stream, between side_start (recorded on `stream` after
@@ -83,12 +156,12 @@ struct gx_engine {
   // (work_cnt[GX_WC_SCANS]) read back without stalling the device: a snapshot is copied to pinned
   // memory every second round and consumed two snapshots later (scan_probe_begin). Both placements give
   // the same results; only the time differs.
-  bool scan_heavy;
+  bool scan_heavy = true;  // k_scan placement until the first snapshots say no view gets scanned
   uint64_t *scan_snap;      // [2 + GX_QUIET_SLOTS] pinned host copies of (tag << 32 | a work_cnt word), written by
                             // k_send: [0..1] work_cnt[GX_WC_SCANS] tagged with the round, then quiet-round
                             // bounds (quiet_probe)
   uint64_t *scan_snap_dev;  // the same memory as the device addresses it
-  uint32_t scan_tag[2];     // the round each slot's snapshot was asked for
+  uint32_t scan_tag[2] = {~0u, ~0u};  // the round each slot's snapshot was asked for
   uint32_t scan_k, scan_last;
   // Quiet rounds (quiet_round): every round from now until quiet_until is quiet, by the
   // bounds the device has reported through scan_snap[2..]. quiet_tag: the snapshot each slot was asked
@@ -141,9 +214,9 @@ struct gx_engine {
   std::vector<uint32_t> pack_gstart;  // pack index range per destination shard
   std::vector<uint64_t> delta_off_h;
   uint64_t delta_total, lead_in_total, ret_total;
-  int ae_delta_round, ae_ret_round;
-  int ae_planned_round;
-  int64_t ae_local_round;
+  int ae_delta_round = -1, ae_ret_round = -1;
+  int ae_planned_round = -1;
+  int64_t ae_local_round = -1;
   // listeners: host-side channels fed from the per-view device event logs
   struct Listener {
     uint32_t view, id, cap;
@@ -153,8 +226,7 @@ struct gx_engine {
   std::vector<uint32_t> log_views;  // view of each device event log
   uint64_t listener_drops;
   // small device scratch for single-host ABI calls
-  void *api_dev;
-  size_t api_dev_bytes;
+  DevBuf api;
   unsigned long long *conv_bad;
   uint64_t *digest_buf;
   size_t kprof_n;  // diagnostics: u64 marks in d.kprof (env GX_KPROF)
@@ -163,11 +235,11 @@ struct gx_engine {
   hipStream_t xplan_stream;
   uint32_t *xplan_dev;           // [2][XPLAN_BATCH][G][G] (k_send of a packing round reads its row)
   uint32_t *xplan_host;          // [2][XPLAN_BATCH][G][G] pinned
-  int64_t xplan_start[2];
+  int64_t xplan_start[2] = {-1, -1};
   uint64_t xplan_waits[2];       // diagnostics: calls whose batch was not ready yet (a host wait) / all calls
   hipEvent_t xplan_ev[2];
   hipEvent_t xplan_join;         // a batch is rewritten after the rounds queued before it (xplan_launch)
-  int64_t xbound_round;          // the round xbound holds
+  int64_t xbound_round = -1;     // the round xbound holds
   XBound xbound;                 // this shard's slots per destination this round
   const uint32_t *xbound_dev;    // the same row on the device
   uint32_t *ob_claim;            // Dev::ob_claim (gx_round_gossip_begin packing in k_send)
@@ -181,15 +253,8 @@ struct gx_engine {
 static void codec_free(gx_engine *e);  // gx_codec_host.hpp
 
 static int ensure_api(gx_engine *e, size_t bytes) {
-  if (bytes <= e->api_dev_bytes) return GX_OK;
-  if (e->api_dev) (void)hipFree(e->api_dev);
-  e->api_dev = nullptr;
-  e->api_dev_bytes = 0;
-  size_t b = 1 << 20;
-  while (b < bytes) b <<= 1;
-  HIPCHK(hipMalloc(&e->api_dev, b));
-  e->api_dev_bytes = b;
-  return GX_OK;
+  void *p;
+  return dbuf(e->api, bytes, &p, 1 << 20);
 }
 
 static bool own(const gx_engine *e, uint32_t v) { return v >= e->d.lo && v < e->d.lo + e->d.Hl; }
@@ -984,100 +1049,24 @@ int gx_destroy(gx_engine *e) {
     (void)hipEventDestroy(t.a);
     (void)hipEventDestroy(t.b);
   }
-  Dev &d = e->d;
-  void *ptrs[] = {e->ae_dig, e->ae_mask, e->ae_fmask, e->ae_lt, e->ae_retL, e->ae_bcnt, e->ae_cnt, e->ae_nfol, e->ae_sz, e->ae_off, e->ae_rioff, e->ae_err, d.msg_key, d.in_stamp, e->ob_entries, e->ob_counts, e->ob_total, e->ob_claim, e->ae_pa, e->ae_pb, e->ae_pack_host, e->ae_pack_t, e->ae_pack_other, e->ae_pack_first, e->ae_skip, e->fd_rsnap, e->ae_prow,
-                  e->ae_pcount, d.view, d.minexp, d.own_status, d.hs, d.fifo, d.sleep, d.dq, d.arena, d.arena_len, d.msg, d.msg_w0, d.msg_len,
-                  d.msg_dst, e->in_cnt_buf, d.scan_list, d.scan_cnt, d.tick,
-                  d.sbytes, d.srvt, d.vlc, d.ev_slot, d.ev_log, d.ev_cnt, d.ctr, d.in_hdr, d.in_ovf, d.in_rec, d.work_cnt, d.quiet_w, d.work, d.mrec, e->pp_dev, e->pp_prow, e->name_rank, e->api_dev, e->conv_bad, e->digest_buf, d.kprof,
-                  d.mem, d.fd_dl, d.fdh, d.fdm, d.fd_len, d.fd_peers, d.fd_np, d.fd_snap, d.lkb, d.pexp, d.dpool, d.dpool_host, d.dpool_res, d.ro_flag, d.ro_list, d.dslot, d.claim_bits, d.ro_n, d.fdq};
-  for (void *p : ptrs)
-    if (p) (void)hipFree(p);
+  e->mem.release();
   codec_free(e);
+  // what is not hipMalloc memory
   if (e->own_stream) (void)hipStreamDestroy(e->own_stream);
   if (e->side_stream) (void)hipStreamDestroy(e->side_stream);
-  if (e->side_start) (void)hipEventDestroy(e->side_start);
-  if (e->side_done) (void)hipEventDestroy(e->side_done);
-  if (e->scan_snap) (void)hipHostFree(e->scan_snap);
-  if (e->xplan_dev) (void)hipFree(e->xplan_dev);
-  if (e->scan_tmp) (void)hipFree(e->scan_tmp);
-  if (e->scan_chunk) (void)hipFree(e->scan_chunk);
-  if (e->xplan_host) (void)hipHostFree(e->xplan_host);
-  for (int i = 0; i < 2; i++)
-    if (e->xplan_ev[i]) (void)hipEventDestroy(e->xplan_ev[i]);
-  if (e->xplan_join) (void)hipEventDestroy(e->xplan_join);
   if (e->xplan_stream) (void)hipStreamDestroy(e->xplan_stream);
-  delete e;
+  for (hipEvent_t ev : {e->side_start, e->side_done, e->xplan_ev[0], e->xplan_ev[1], e->xplan_join})
+    if (ev) (void)hipEventDestroy(ev);
+  if (e->scan_snap) (void)hipHostFree(e->scan_snap);
+  if (e->xplan_host) (void)hipHostFree(e->xplan_host);
+  delete e;  // with the api scratch (DevBuf)
   return GX_OK;
 }
 
-#define ALLOC(ptr, bytes)                                   \
-  do {                                                      \
-    if (hipMalloc((void **)&(ptr), (bytes)) != hipSuccess) { \
-      (void)hipGetLastError();                              \
-      gx_destroy(e);                                        \
-      return GX_ENOMEM;                                     \
-    }                                                       \
-  } while (0)
-
-int gx_create(const gx_params *p, gx_engine **out) {
-  if (!out) return GX_EINVAL;
-  int rc = check_params(p);
-  if (rc) return rc;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || p->device < 0 || p->device >= ndev) return GX_EIO;
-  HIPCHK(hipSetDevice(p->device));
-  gx_engine *e = new gx_engine();
-  memset(&e->d, 0, sizeof(e->d));
-  e->device = p->device;
-  e->timing = 0;
-  memset(e->ms, 0, sizeof(e->ms));
-  memset(e->launches, 0, sizeof(e->launches));
-  memset(e->host_bytes, 0, sizeof(e->host_bytes));
-  memset(e->host_units, 0, sizeof(e->host_units));
-  e->codec = nullptr;
-  e->api_dev = nullptr;
-  e->api_dev_bytes = 0;
-  e->conv_bad = nullptr;
-  e->digest_buf = nullptr;
-  e->stream = e->own_stream = e->side_stream = nullptr;
-  e->in_cnt_buf = nullptr;
-  e->side_start = e->side_done = nullptr;
-  e->side_pending = false;
-  e->scan_heavy = true;  // k_scan placement until the first snapshots say no view gets scanned
-  e->scan_snap = e->scan_snap_dev = nullptr;
-  memset(e->quiet_tag, 0, sizeof(e->quiet_tag));
-  e->quiet_seq = 0;
-  e->quiet_nowait = false;
-  e->quiet_until = e->quiet_from = 0;
-  e->quiet_now = false;
-  e->scan_tag[0] = e->scan_tag[1] = 0xffffffffu;
-  e->scan_k = e->scan_last = 0;
-  e->async_phases = 0;
-  e->ob_entries = nullptr;
-  e->ob_counts = nullptr;
-  e->n_ob = 0;
-  e->ob_async = false;
-  e->ob_total = nullptr;
-  e->ob_claim = nullptr;
-  e->ae_pa = e->ae_pb = e->ae_pack_host = e->ae_pack_t = e->ae_pack_other = nullptr;
-  e->ae_pack_first = e->ae_skip = nullptr;
-  e->fd_rsnap = nullptr;
-  e->ae_prow = nullptr;
-  e->ae_pcount = nullptr;
-  e->ae_dig = nullptr;
-  e->ae_mask = e->ae_fmask = e->ae_cnt = e->ae_nfol = e->ae_err = nullptr;
-  e->ae_lt = nullptr;
-  e->ae_retL = nullptr;
-  e->ae_bcnt = nullptr;
-  e->ae_sz = e->ae_off = e->ae_rioff = nullptr;
-  e->ae_delta_round = e->ae_ret_round = -1;
-  e->delta_total = e->lead_in_total = e->ret_total = 0;
-  e->n_plan = e->n_pack = e->n_plan_rows = 0;
-  e->ae_planned_round = -1;
-  e->ae_local_round = -1;
-  e->pp_dev = nullptr;
-  e->pp_prow = nullptr;
-  e->name_rank = nullptr;
+// ------------------------------------------------------------------------------ gx_create --
+// Its steps. A step that fails returns at once: gx_create destroys the engine with whatever the
+// steps made so far.
+static void create_dims(gx_engine *e, const gx_params *p) {
   Dev &d = e->d;
   d.p = *p;
   d.epoch = gx_epoch_of(p->t0_ns);
@@ -1087,58 +1076,20 @@ int gx_create(const gx_params *p, gx_engine **out) {
   d.R = p->n_hosts * p->n_services;
   d.Q = p->queue_cap;
   d.A = p->list_slots;
+  d.AW = (d.A + 31) / 32;
   d.L = p->packet_cap + p->pending_cap;
   d.K = p->fanout;
   d.NG = p->gossip_messages > 1 ? p->gossip_messages : 1;
   d.KG = d.K * d.NG;
   d.KE = d.KG + (p->probe_piggyback ? 2u : 0u);  // the probe ping and ack entries (gx.h probe_piggyback)
   d.divS = d.S > 1 ? ~0ull / d.S + 1 : 0;
-  d.logS = 0;
   while ((1u << d.logS) < d.S) d.logS++;  // used where S divides 64 (a power of two)
   d.G = p->n_shards > 1 ? p->n_shards : 1;
   d.gid = d.G > 1 ? p->shard_id : 0;
   d.lo = (uint32_t)(((uint64_t)d.gid * d.H) / d.G);
   d.Hl = (uint32_t)(((uint64_t)(d.gid + 1) * d.H) / d.G) - d.lo;
-  d.n_remote = 0;
   d.SQ = pow2_at_least(64 > d.KE * (p->retransmit_rounds + 1) ? 64 : d.KE * (p->retransmit_rounds + 1));
   d.DQ = pow2_at_least(d.L + p->pending_cap + 64);
-  d.round = 0;
-  if (hipStreamCreateWithFlags(&e->own_stream, hipStreamNonBlocking) != hipSuccess) {
-    delete e;
-    return GX_EIO;
-  }
-  e->stream = e->own_stream;
-  e->async_phases = 0;
-  if (hipStreamCreateWithFlags(&e->side_stream, hipStreamNonBlocking) != hipSuccess ||
-      hipEventCreateWithFlags(&e->side_start, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&e->side_done, hipEventDisableTiming) != hipSuccess ||
-      hipHostMalloc((void **)&e->scan_snap, (2 + GX_QUIET_SLOTS) * sizeof(uint64_t), hipHostMallocMapped) != hipSuccess ||
-      hipHostGetDevicePointer((void **)&e->scan_snap_dev, e->scan_snap, 0) != hipSuccess) {
-    (void)hipGetLastError();
-    gx_destroy(e);
-    return GX_EIO;
-  }
-  e->scan_snap[0] = e->scan_snap[1] = ~0ull;
-  for (int i = 0; i < GX_QUIET_SLOTS; i++) e->scan_snap[2 + i] = 0;
-  // per-host arrays hold this shard's Hl hosts; the message table also takes the packets received
-  // from other shards (at most (H - Hl) * K), so it is sized H * K.
-  size_t Hg = d.H, H = d.Hl, K = d.KE ? d.KE : 1;
-  ALLOC(d.view, sizeof(uint64_t) * H * d.R);
-  ALLOC(d.own_status, H * d.S);
-  ALLOC(d.hs, sizeof(gx_host_state) * H);
-  ALLOC(d.fifo, sizeof(gx_job) * H * d.Q);
-  ALLOC(d.sleep, sizeof(gx_sleeper) * H * d.SQ);
-  ALLOC(d.dq, sizeof(grec) * H * d.DQ);
-  ALLOC(d.arena, sizeof(grec) * H * d.A * d.L);
-  ALLOC(d.arena_len, sizeof(uint32_t) * H * d.A);
-  d.AW = (d.A + 31) / 32;
-  ALLOC(d.arena_bits, sizeof(uint32_t) * H * d.AW);
-  ALLOC(d.msg, sizeof(grec) * Hg * K * p->packet_cap);
-  ALLOC(d.msg_w0, sizeof(uint64_t) * Hg * K * p->packet_cap);
-  ALLOC(d.msg_len, sizeof(uint32_t) * Hg * K);
-  ALLOC(d.msg_dst, sizeof(uint32_t) * Hg * K);
-  ALLOC(d.msg_key, sizeof(uint32_t) * Hg * K);
-  ALLOC(e->in_cnt_buf, sizeof(uint32_t) * 2 * H);
   d.nblk_ae = (d.R + GX_DIGEST_SLOTS - 1) / GX_DIGEST_SLOTS;
   // default: 64 slots; with GossipMessages > 1 (up to NG packets per sender) GX_DI_MAX, so the
   // wave merge takes the wide inboxes instead of the serial overflow path
@@ -1147,154 +1098,182 @@ int gx_create(const gx_params *p, gx_engine **out) {
   // senders read their local receivers' view slots and drop no-op records; packets from other
   // shards are filtered the same way on arrival (k_inbox_unpack)
   d.sfilt = 1u;
-  ALLOC(d.in_hdr, sizeof(uint4) * H * d.DI);
-  ALLOC(d.in_ovf, sizeof(uint4) * Hg * K);
-  ALLOC(d.in_rec, sizeof(grec) * H * d.DR * p->packet_cap);
-  ALLOC(d.work_cnt, sizeof(uint32_t) * GX_WC_N);
-  d.QW = 4 * nblk(H ? H : 1, 64);  // k_send's waves (launch_send: 64 hosts per 256-thread block)
-  ALLOC(d.quiet_w, sizeof(uint32_t) * 2 * d.QW);
-  ALLOC(d.work, sizeof(uint32_t) * H);
-  if (p->push_pull_mode == GX_PP_INITIATE) {
-    ALLOC(e->pp_dev, sizeof(uint32_t) * 2 * Hg);
-    ALLOC(e->pp_prow, sizeof(int32_t) * Hg);
-    HIPCHK(hipMemset(e->pp_prow, 0xff, sizeof(int32_t) * Hg));
+  d.QW = 4 * nblk(d.Hl ? d.Hl : 1, 64);  // k_send's waves (launch_send: 64 hosts per 256-thread block)
+  d.departures = p->depart_round >= 0 && p->depart_ppm;
+  if (p->lock_model) {  // gx.h lock_model, lock_readers, fd_handoff_shared
+    d.C = p->lock_buffer;
+    d.PW = (d.H + 31) / 32;
+    if (p->lock_readers) d.P = p->lock_defer_slots ? p->lock_defer_slots : 64;
+    // the handoff queue's places after the 53 the handler's chain holds
+    if (p->fd_handoff_shared) d.HQ = d.C > GX_LOCK_HANDLER_AT ? d.C - GX_LOCK_HANDLER_AT : 0;
   }
-  ALLOC(d.mrec, sizeof(uint32_t) * H);
-  HIPCHK(hipMemset(d.mrec, 0, sizeof(uint32_t) * H));
-  ALLOC(d.minexp, sizeof(unsigned long long) * H);
-  ALLOC(d.scan_list, sizeof(grec) * H * d.L);
-  ALLOC(d.scan_cnt, sizeof(uint32_t) * H);
   // worklist scans split rows of at least 64K slots into chunks of >= 32K (S | 128: owners never
   // straddle a chunk; the split path runs without listeners)
   e->scan_nch = 1;
-  if (d.R >= 65536 && d.S >= 2 && 128 % d.S == 0) {
+  if (d.R >= 65536 && d.S >= 2 && 128 % d.S == 0)
     e->scan_nch = d.R / 32768 < 16 ? d.R / 32768 : 16;  // the most chunks a row takes (scan_chunks)
-    ALLOC(e->scan_tmp, sizeof(grec) * H * e->scan_nch * d.L);
-    ALLOC(e->scan_chunk, sizeof(ScanChunk) * H * e->scan_nch);
+  if (getenv("GX_KPROF"))  // diagnostics: phase marks of every k_send wave (gx_kprof_read)
+    e->kprof_n = (size_t)nblk(d.Hl, 64) * 4 * 8 + GX_KPROF_MERGE_N + 3ull * d.H;  // + merge counts + push-pull blocks + scans
+  if (d.G > 1) {
+    e->nblk = d.nblk_ae;
+    e->nmw = (e->nblk + 31) / 32;
   }
-  ALLOC(d.tick, H);
-  ALLOC(d.sbytes, sizeof(uint16_t) * d.R);
-  ALLOC(d.srvt, sizeof(gx_server_times) * H * Hg);
-  ALLOC(d.vlc, sizeof(int64_t) * H);
-  ALLOC(d.ev_slot, sizeof(int32_t) * H);
-  ALLOC(d.ctr, sizeof(DevCtr));
-  d.departures = p->depart_round >= 0 && p->depart_ppm;
+}
+
+static int create_streams(gx_engine *e) {
+  HIPCHK(hipStreamCreateWithFlags(&e->own_stream, hipStreamNonBlocking));
+  e->stream = e->own_stream;
+  HIPCHK(hipStreamCreateWithFlags(&e->side_stream, hipStreamNonBlocking));
+  HIPCHK(hipEventCreateWithFlags(&e->side_start, hipEventDisableTiming));
+  HIPCHK(hipEventCreateWithFlags(&e->side_done, hipEventDisableTiming));
+  HIPCHK(hipHostMalloc((void **)&e->scan_snap, (2 + GX_QUIET_SLOTS) * sizeof(uint64_t), hipHostMallocMapped));
+  HIPCHK(hipHostGetDevicePointer((void **)&e->scan_snap_dev, e->scan_snap, 0));
+  e->scan_snap[0] = e->scan_snap[1] = ~0ull;
+  for (int i = 0; i < GX_QUIET_SLOTS; i++) e->scan_snap[2 + i] = 0;
+  return GX_OK;
+}
+
+// TAKE(ptr, bytes[, fill byte, s]): one engine buffer, filled on the engine's stream
+#define TAKE(...) GXTRY(e->mem.take(__VA_ARGS__))
+
+static int create_buffers(gx_engine *e) {
+  Dev &d = e->d;
+  const gx_params *p = &d.p;
+  hipStream_t s = e->stream;
+  // per-host arrays hold this shard's Hl hosts; the message table also takes the packets received
+  // from other shards (at most (H - Hl) * K), so it is sized H * K.
+  const size_t Hg = d.H, H = d.Hl, K = d.KE ? d.KE : 1;
+  TAKE(d.view, sizeof(uint64_t) * H * d.R);
+  TAKE(d.own_status, H * d.S);
+  TAKE(d.hs, sizeof(gx_host_state) * H);
+  TAKE(d.fifo, sizeof(gx_job) * H * d.Q);
+  TAKE(d.sleep, sizeof(gx_sleeper) * H * d.SQ);
+  TAKE(d.dq, sizeof(grec) * H * d.DQ);
+  TAKE(d.arena, sizeof(grec) * H * d.A * d.L);
+  TAKE(d.arena_len, sizeof(uint32_t) * H * d.A, 0, s);
+  TAKE(d.arena_bits, sizeof(uint32_t) * H * d.AW);
+  TAKE(d.msg, sizeof(grec) * Hg * K * p->packet_cap);
+  TAKE(d.msg_w0, sizeof(uint64_t) * Hg * K * p->packet_cap);
+  TAKE(d.msg_len, sizeof(uint32_t) * Hg * K, 0, s);
+  TAKE(d.msg_dst, sizeof(uint32_t) * Hg * K);
+  TAKE(d.msg_key, sizeof(uint32_t) * Hg * K);
+  TAKE(e->in_cnt_buf, sizeof(uint32_t) * 2 * H, 0, s);
+  TAKE(d.in_hdr, sizeof(uint4) * H * d.DI);
+  TAKE(d.in_ovf, sizeof(uint4) * Hg * K);
+  TAKE(d.in_rec, sizeof(grec) * H * d.DR * p->packet_cap);
+  TAKE(d.work_cnt, sizeof(uint32_t) * GX_WC_N, 0, s);
+  TAKE(d.quiet_w, sizeof(uint32_t) * 2 * d.QW, 0, s);  // (0: no round is quiet)
+  TAKE(d.work, sizeof(uint32_t) * H);
+  if (p->push_pull_mode == GX_PP_INITIATE) {
+    TAKE(e->pp_dev, sizeof(uint32_t) * 2 * Hg);
+    TAKE(e->pp_prow, sizeof(int32_t) * Hg, 0xff, s);
+  }
+  TAKE(d.mrec, sizeof(uint32_t) * H, 0, s);
+  TAKE(d.minexp, sizeof(unsigned long long) * H);
+  TAKE(d.scan_list, sizeof(grec) * H * d.L);
+  TAKE(d.scan_cnt, sizeof(uint32_t) * H);
+  if (e->scan_nch > 1) {
+    TAKE(e->scan_tmp, sizeof(grec) * H * e->scan_nch * d.L);
+    TAKE(e->scan_chunk, sizeof(ScanChunk) * H * e->scan_nch);
+  }
+  TAKE(d.tick, H, 0, s);
+  TAKE(d.sbytes, sizeof(uint16_t) * d.R);
+  TAKE(d.srvt, sizeof(gx_server_times) * H * Hg);
+  TAKE(d.vlc, sizeof(int64_t) * H);
+  TAKE(d.ev_slot, sizeof(int32_t) * H, 0xff, s);  // -1: no listener
+  TAKE(d.ctr, sizeof(DevCtr), 0, s);
   if (p->fd_enable) {  // member rows of this shard's hosts
-    ALLOC(d.mem, sizeof(gx_member) * H * Hg);
-    ALLOC(d.fd_dl, sizeof(int32_t) * H * Hg);
-    ALLOC(d.fdh, sizeof(gx_fd_host) * H);
-    ALLOC(d.fdm, sizeof(gx_fd_msg) * Hg * K * p->fd_msg_cap);
-    ALLOC(d.fd_len, sizeof(uint32_t) * Hg * K);
-    ALLOC(d.fd_peers, sizeof(uint32_t) * H * K);
-    ALLOC(d.fd_np, sizeof(uint32_t) * H);
-    if (p->fd_push_pull_state) ALLOC(d.fd_snap, sizeof(uint64_t) * H * Hg);
+    TAKE(d.mem, sizeof(gx_member) * H * Hg);
+    TAKE(d.fd_dl, sizeof(int32_t) * H * Hg);
+    TAKE(d.fdh, sizeof(gx_fd_host) * H);
+    TAKE(d.fdm, sizeof(gx_fd_msg) * Hg * K * p->fd_msg_cap);
+    TAKE(d.fd_len, sizeof(uint32_t) * Hg * K, 0, s);
+    TAKE(d.fd_peers, sizeof(uint32_t) * H * K);
+    TAKE(d.fd_np, sizeof(uint32_t) * H);
+    if (p->fd_push_pull_state) TAKE(d.fd_snap, sizeof(uint64_t) * H * Hg);
   }
   if (p->lock_model) {  // locked hosts' inbound pipelines and waiting ExpireServer calls (gx.h lock_model)
-    d.C = p->lock_buffer;
-    ALLOC(d.lkb, sizeof(grec) * H * d.C);
-    d.PW = (d.H + 31) / 32;
-    if (p->storm_round >= 0 || p->fd_enable) {
-      ALLOC(d.pexp, sizeof(uint32_t) * H * d.PW);
-      HIPCHK(hipMemset(d.pexp, 0, sizeof(uint32_t) * H * d.PW));
-    }
+    TAKE(d.lkb, sizeof(grec) * H * d.C);
+    if (p->storm_round >= 0 || p->fd_enable) TAKE(d.pexp, sizeof(uint32_t) * H * d.PW, 0, s);
     if (p->lock_readers) {  // the waiting push-pull merges' pool (gx.h lock_readers)
-      d.P = p->lock_defer_slots ? p->lock_defer_slots : 64;
-      ALLOC(d.dpool, sizeof(uint64_t) * d.P * d.R);
-      ALLOC(d.dpool_host, sizeof(uint32_t) * d.P);
-      ALLOC(d.dpool_res, sizeof(uint32_t) * d.P);
-      ALLOC(d.ro_flag, H);
-      ALLOC(d.ro_list, sizeof(uint32_t) * H);
-      ALLOC(d.ro_n, sizeof(uint32_t));
-      ALLOC(d.dslot, sizeof(uint32_t) * Hg);  // each host's slot, the claimants' bits
-      ALLOC(d.claim_bits, sizeof(uint32_t) * ((Hg + 31) / 32));
-      HIPCHK(hipMemset(d.dpool_host, 0xff, sizeof(uint32_t) * d.P));
-      HIPCHK(hipMemset(d.dpool_res, 0, sizeof(uint32_t) * d.P));
-      HIPCHK(hipMemset(d.ro_flag, 0, H));
-      HIPCHK(hipMemset(d.ro_n, 0, sizeof(uint32_t)));
-      HIPCHK(hipMemset(d.dslot, 0xff, sizeof(uint32_t) * Hg));
-      HIPCHK(hipMemset(d.claim_bits, 0, sizeof(uint32_t) * ((Hg + 31) / 32)));
+      TAKE(d.dpool, sizeof(uint64_t) * d.P * d.R);
+      TAKE(d.dpool_host, sizeof(uint32_t) * d.P, 0xff, s);
+      TAKE(d.dpool_res, sizeof(uint32_t) * d.P, 0, s);
+      TAKE(d.ro_flag, H, 0, s);
+      TAKE(d.ro_list, sizeof(uint32_t) * H);
+      TAKE(d.ro_n, sizeof(uint32_t), 0, s);
+      TAKE(d.dslot, sizeof(uint32_t) * Hg, 0xff, s);  // each host's slot, the claimants' bits
+      TAKE(d.claim_bits, sizeof(uint32_t) * ((Hg + 31) / 32), 0, s);
     }
-    if (p->fd_handoff_shared) {  // the handoff queue's places after the 53 the handler's chain holds
-      d.HQ = d.C > GX_LOCK_HANDLER_AT ? d.C - GX_LOCK_HANDLER_AT : 0;
-      ALLOC(d.fdq, sizeof(gx_fd_msg) * H * (d.HQ ? d.HQ : 1));
-    }
+    if (p->fd_handoff_shared) TAKE(d.fdq, sizeof(gx_fd_msg) * H * (d.HQ ? d.HQ : 1));
   }
-  ALLOC(e->conv_bad, sizeof(unsigned long long));
-  e->xplan_stream = nullptr;
-  e->xplan_dev = e->xplan_host = nullptr;
-  e->xplan_start[0] = e->xplan_start[1] = -1;
-  e->xplan_waits[0] = e->xplan_waits[1] = 0;
-  e->xplan_ev[0] = e->xplan_ev[1] = nullptr;
-  e->xplan_join = nullptr;
-  e->xbound_round = -1;
-  e->xbound_dev = nullptr;
-  e->kprof_n = 0;
-  if (getenv("GX_KPROF")) {  // diagnostics: phase marks of every k_send wave (gx_kprof_read)
-    e->kprof_n = (size_t)nblk(d.Hl, 64) * 4 * 8 + GX_KPROF_MERGE_N + 3ull * d.H;  // + merge counts + push-pull blocks + scans
-    ALLOC(d.kprof, sizeof(unsigned long long) * e->kprof_n);
-    HIPCHK(hipMemset(d.kprof, 0, sizeof(unsigned long long) * e->kprof_n));
-  }
-  ALLOC(e->digest_buf, sizeof(uint64_t) * H);
+  TAKE(e->conv_bad, sizeof(unsigned long long));
+  if (e->kprof_n) TAKE(d.kprof, sizeof(unsigned long long) * e->kprof_n, 0, s);
+  TAKE(e->digest_buf, sizeof(uint64_t) * H);
   if (d.G > 1) {
-    ALLOC(e->ob_entries, sizeof(uint32_t) * H * K);
-    ALLOC(d.in_stamp, sizeof(uint32_t) * Hg * K);
-    HIPCHK(hipMemset(d.in_stamp, 0, sizeof(uint32_t) * Hg * K));
-    ALLOC(e->ob_total, sizeof(uint32_t));
-    ALLOC(e->ob_claim, sizeof(uint32_t) * (XPLAN_GMAX + 1));
-    HIPCHK(hipMemset(e->ob_claim, 0, sizeof(uint32_t) * (XPLAN_GMAX + 1)));
-    ALLOC(e->ob_counts, sizeof(uint32_t) * p->n_shards * (1 + 2 * ((H * K + 255) / 256)));
-    size_t np = Hg / 2 + 1;
-    ALLOC(e->ae_pa, sizeof(uint32_t) * np);
-    ALLOC(e->ae_pb, sizeof(uint32_t) * np);
-    ALLOC(e->ae_prow, sizeof(int32_t) * np);
-    ALLOC(e->ae_pcount, np);
-    ALLOC(e->ae_pack_host, sizeof(uint32_t) * np);
-    ALLOC(e->ae_pack_t, sizeof(uint32_t) * np);
-    ALLOC(e->ae_pack_other, sizeof(uint32_t) * np);
-    ALLOC(e->ae_pack_first, np);
-    ALLOC(e->ae_skip, np);
-    if (p->fd_enable && p->fd_push_pull_state) ALLOC(e->fd_rsnap, sizeof(uint64_t) * np * Hg);
-    e->nblk = (d.R + GX_DIGEST_SLOTS - 1) / GX_DIGEST_SLOTS;
-    e->nmw = (e->nblk + 31) / 32;
-    ALLOC(e->ae_dig, sizeof(ulonglong2) * H * e->nblk);
-    ALLOC(e->ae_mask, sizeof(uint32_t) * H * e->nmw);
-    ALLOC(e->ae_fmask, sizeof(uint32_t) * H * e->nmw);
-    ALLOC(e->ae_lt, sizeof(uint16_t) * H * e->nblk);
-    ALLOC(e->ae_retL, sizeof(uint16_t) * H * e->nblk);
-    ALLOC(e->ae_bcnt, sizeof(uint32_t) * H * e->nblk);
-    ALLOC(e->ae_cnt, sizeof(uint32_t) * H);
-    ALLOC(e->ae_nfol, sizeof(uint32_t) * H);
-    ALLOC(e->ae_sz, sizeof(uint64_t) * 4 * H);
-    ALLOC(e->ae_off, sizeof(uint64_t) * 4 * H);
-    ALLOC(e->ae_rioff, sizeof(uint64_t) * H);
-    ALLOC(e->ae_err, sizeof(uint32_t));
+    TAKE(e->ob_entries, sizeof(uint32_t) * H * K);
+    TAKE(d.in_stamp, sizeof(uint32_t) * Hg * K, 0, s);
+    TAKE(e->ob_total, sizeof(uint32_t));
+    TAKE(e->ob_claim, sizeof(uint32_t) * (XPLAN_GMAX + 1), 0, s);
+    TAKE(e->ob_counts, sizeof(uint32_t) * d.G * (1 + 2 * ((H * K + 255) / 256)));
+    const size_t np = Hg / 2 + 1;
+    TAKE(e->ae_pa, sizeof(uint32_t) * np);
+    TAKE(e->ae_pb, sizeof(uint32_t) * np);
+    TAKE(e->ae_prow, sizeof(int32_t) * np);
+    TAKE(e->ae_pcount, np);
+    TAKE(e->ae_pack_host, sizeof(uint32_t) * np);
+    TAKE(e->ae_pack_t, sizeof(uint32_t) * np);
+    TAKE(e->ae_pack_other, sizeof(uint32_t) * np);
+    TAKE(e->ae_pack_first, np);
+    TAKE(e->ae_skip, np);
+    if (pp_state(d)) TAKE(e->fd_rsnap, sizeof(uint64_t) * np * Hg);
+    TAKE(e->ae_dig, sizeof(ulonglong2) * H * e->nblk);
+    TAKE(e->ae_mask, sizeof(uint32_t) * H * e->nmw);
+    TAKE(e->ae_fmask, sizeof(uint32_t) * H * e->nmw);
+    TAKE(e->ae_lt, sizeof(uint16_t) * H * e->nblk);
+    TAKE(e->ae_retL, sizeof(uint16_t) * H * e->nblk);
+    TAKE(e->ae_bcnt, sizeof(uint32_t) * H * e->nblk);
+    TAKE(e->ae_cnt, sizeof(uint32_t) * H);
+    TAKE(e->ae_nfol, sizeof(uint32_t) * H);
+    TAKE(e->ae_sz, sizeof(uint64_t) * 4 * H);
+    TAKE(e->ae_off, sizeof(uint64_t) * 4 * H);
+    TAKE(e->ae_rioff, sizeof(uint64_t) * H);
+    TAKE(e->ae_err, sizeof(uint32_t));
   }
+  return GX_OK;
+}
+#undef TAKE
+
+static int create_init(gx_engine *e) {
+  Dev &d = e->d;
   hipStream_t s = e->stream;
-  uint64_t *rec_word = nullptr;
-  ALLOC(rec_word, sizeof(uint64_t) * d.R);
-  HIPCHK(hipMemsetAsync(d.ctr, 0, sizeof(DevCtr), s));
+  DevMem tmp;  // freed on every return, after sync_check has waited for the kernels
+  uint64_t *rec_word;
+  GXTRY(tmp.take(rec_word, sizeof(uint64_t) * d.R));
   HIPCHK(hipMemsetAsync(d.ctr->first_drop, 0xff, sizeof(d.ctr->first_drop), s));  // min: none yet
-  HIPCHK(hipMemsetAsync(d.arena_len, 0, sizeof(uint32_t) * H * d.A, s));
-  HIPCHK(hipMemsetAsync(d.msg_len, 0, sizeof(uint32_t) * Hg * K, s));
-  HIPCHK(hipMemsetAsync(e->in_cnt_buf, 0, sizeof(uint32_t) * 2 * H, s));
-  HIPCHK(hipMemsetAsync(d.work_cnt, 0, sizeof(uint32_t) * GX_WC_N, s));
-  HIPCHK(hipMemsetAsync(d.quiet_w, 0, sizeof(uint32_t) * 2 * d.QW, s));  // (0: no round is quiet)
-  HIPCHK(hipMemsetAsync(d.tick, 0, H, s));
-  HIPCHK(hipMemsetAsync(d.ev_slot, 0xff, sizeof(int32_t) * H, s));  // -1: no listener
   k_fill_u16<<<256, 256, 0, s>>>(d.sbytes, d.R, (uint16_t)GX_STATIC_BYTES_DEFAULT);
   set_round_fields(e);
   k_init_rec<<<nblk(d.R, 256), 256, 0, s>>>(d, rec_word);
   k_init_views<<<2048, 256, 0, s>>>(d, rec_word);
   k_init_times<<<2048, 256, 0, s>>>(d, rec_word);
   k_init_hosts<<<nblk(d.Hl, 256), 256, 0, s>>>(d);
-  if (p->fd_enable) {
-    k_fd_init<<<2048, 256, 0, s>>>(d);
-    HIPCHK(hipMemsetAsync(d.fd_len, 0, sizeof(uint32_t) * Hg * K, s));
-  }
+  if (d.p.fd_enable) k_fd_init<<<2048, 256, 0, s>>>(d);
   k_minexp_recompute<<<d.Hl, 256, 0, s>>>(d, 0);
-  rc = sync_check(e);
-  (void)hipFree(rec_word);
-  if (rc) {
+  return sync_check(e);
+}
+
+int gx_create(const gx_params *p, gx_engine **out) {
+  if (!out) return GX_EINVAL;
+  int rc = check_params(p);
+  if (rc) return rc;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || p->device < 0 || p->device >= ndev) return GX_EIO;
+  HIPCHK(hipSetDevice(p->device));
+  gx_engine *e = new gx_engine();  // value-initialised: zero wherever the struct names no other value
+  e->device = p->device;
+  create_dims(e, p);
+  if ((rc = create_streams(e)) || (rc = create_buffers(e)) || (rc = create_init(e))) {
+    (void)hipGetLastError();
     gx_destroy(e);
     return rc;
   }
@@ -1368,7 +1347,7 @@ static int stage_recs(gx_engine *e, const gx_service *svcs, uint32_t n, size_t o
     if (to_grec(e, &svcs[i], &tmp[i])) return GX_EINVAL;
   int rc = ensure_api(e, offset + sizeof(grec) * (n + 1));
   if (rc) return rc;
-  grec *dev = (grec *)((char *)e->api_dev + offset);
+  grec *dev = (grec *)((char *)e->api.p + offset);
   if (n) HIPCHK(hipMemcpyAsync(dev, tmp.data(), sizeof(grec) * n, hipMemcpyHostToDevice, e->stream));
   *dev_out = dev;
   return GX_OK;
@@ -1390,8 +1369,8 @@ static int api_add(gx_engine *e, const uint32_t *views, uint32_t fixed_view, con
   grec *drec;
   int rc = stage_recs(e, svcs, n, vbytes + 256, &drec);
   if (rc) return rc;
-  uint32_t *dviews = (uint32_t *)e->api_dev;
-  uint32_t *dacc = (uint32_t *)((char *)e->api_dev + vbytes);
+  uint32_t *dviews = (uint32_t *)e->api.p;
+  uint32_t *dacc = (uint32_t *)((char *)e->api.p + vbytes);
   if (views && n) HIPCHK(hipMemcpyAsync(dviews, views, sizeof(uint32_t) * n, hipMemcpyHostToDevice, e->stream));
   set_round_fields(e);
   k_api_add<<<1, 64, 0, e->stream>>>(e->d, views ? dviews : nullptr, fixed_view, drec, n, src, dacc);
@@ -1433,8 +1412,8 @@ int gx_tombstone_others(gx_engine *e, uint32_t view, gx_service *out, uint32_t c
   quiet_invalidate(e);
   int rc = ensure_api(e, 256 + sizeof(grec) * (cap + 1));
   if (rc) return rc;
-  uint32_t *dcnt = (uint32_t *)e->api_dev;
-  grec *dlist = (grec *)((char *)e->api_dev + 256);
+  uint32_t *dcnt = (uint32_t *)e->api.p;
+  grec *dlist = (grec *)((char *)e->api.p + 256);
   set_round_fields(e);
   scan_one_view(e, view, dlist, cap, dcnt);
   uint32_t n = 0;
@@ -1463,9 +1442,9 @@ int gx_tombstone_services(gx_engine *e, uint32_t host, const uint16_t *running, 
   int rc = ensure_api(e, 64);
   if (rc) return rc;
   set_round_fields(e);
-  k_api_tomb<<<1, 64, 0, e->stream>>>(e->d, host, mask, (uint64_t *)e->api_dev);
+  k_api_tomb<<<1, 64, 0, e->stream>>>(e->d, host, mask, (uint64_t *)e->api.p);
   uint64_t m = 0;
-  rc = read_back(e, e->api_dev, &m);
+  rc = read_back(e, e->api.p, &m);
   if (rc) return rc;
   uint32_t n = 0;
   int64_t now = now_of(e);
@@ -1491,9 +1470,9 @@ int gx_expire_server(gx_engine *e, uint32_t view, uint32_t owner, int *expired) 
   int rc = ensure_api(e, 64);
   if (rc) return rc;
   set_round_fields(e);
-  k_api_expire<<<1, 64, 0, e->stream>>>(e->d, view, owner, (uint32_t *)e->api_dev);
+  k_api_expire<<<1, 64, 0, e->stream>>>(e->d, view, owner, (uint32_t *)e->api.p);
   uint32_t x = 0;
-  rc = read_back(e, e->api_dev, &x);
+  rc = read_back(e, e->api.p, &x);
   if (!rc && expired) *expired = (int)x;
   return rc;
 }
@@ -1537,8 +1516,8 @@ int gx_broadcast_tombstones(gx_engine *e, uint32_t host, const gx_service *list,
   quiet_invalidate(e);
   int rc = ensure_api(e, 256 + sizeof(grec) * (e->d.L + 1));
   if (rc) return rc;
-  uint32_t *dcnt = (uint32_t *)e->api_dev;
-  grec *dlist = (grec *)((char *)e->api_dev + 256);
+  uint32_t *dcnt = (uint32_t *)e->api.p;
+  grec *dlist = (grec *)((char *)e->api.p + 256);
   set_round_fields(e);
   scan_one_view(e, host, dlist, e->d.L, dcnt);
   k_api_bt<<<1, 64, 0, e->stream>>>(e->d, host, mask, dlist, dcnt);
@@ -1550,9 +1529,9 @@ int gx_owner_slots_in_use(gx_engine *e, uint32_t owner, uint64_t *mask) {
   HIPCHK(hipSetDevice(e->device));
   int rc = ensure_api(e, 64);
   if (rc) return rc;
-  HIPCHK(hipMemsetAsync(e->api_dev, 0, sizeof(uint64_t), e->stream));
-  k_slots_in_use<<<nblk(e->d.Hl, 256), 256, 0, e->stream>>>(e->d, owner, (unsigned long long *)e->api_dev);
-  HIPCHK(hipMemcpyAsync(mask, e->api_dev, sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipMemsetAsync(e->api.p, 0, sizeof(uint64_t), e->stream));
+  k_slots_in_use<<<nblk(e->d.Hl, 256), 256, 0, e->stream>>>(e->d, owner, (unsigned long long *)e->api.p);
+  HIPCHK(hipMemcpyAsync(mask, e->api.p, sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream));
   return sync_check(e);
 }
 
@@ -1562,9 +1541,9 @@ int gx_is_new_service(gx_engine *e, uint32_t view, const gx_service *svc, int *o
   HIPCHK(hipSetDevice(e->device));
   int rc = ensure_api(e, 64);
   if (rc) return rc;
-  k_api_is_new<<<1, 64, 0, e->stream>>>(e->d, view, g.w, g.r, (uint32_t *)e->api_dev);
+  k_api_is_new<<<1, 64, 0, e->stream>>>(e->d, view, g.w, g.r, (uint32_t *)e->api.p);
   uint32_t x = 0;
-  rc = read_back(e, e->api_dev, &x);
+  rc = read_back(e, e->api.p, &x);
   if (!rc) *out = (int)x;
   return rc;
 }
@@ -1575,8 +1554,8 @@ static int getb_impl(gx_engine *e, uint32_t host, uint32_t limit, uint32_t limit
   quiet_invalidate(e);
   int rc = ensure_api(e, 256 + sizeof(grec) * (limit + 1));
   if (rc) return rc;
-  uint32_t *dn = (uint32_t *)e->api_dev;
-  grec *dpk = (grec *)((char *)e->api_dev + 256);
+  uint32_t *dn = (uint32_t *)e->api.p;
+  grec *dpk = (grec *)((char *)e->api.p + 256);
   set_round_fields(e);
   k_api_getb<<<1, 64, 0, e->stream>>>(e->d, host, limit, dpk, dn, limit_bytes, overhead);
   uint32_t n = 0;
@@ -1626,7 +1605,7 @@ int gx_message_bytes(gx_engine *e, const gx_service *recs, uint32_t n, uint32_t 
   HIPCHK(hipSetDevice(e->device));
   int rc = ensure_api(e, 256 + (sizeof(grec) + sizeof(uint32_t)) * (size_t)n);
   if (rc) return rc;
-  grec *dg = (grec *)((char *)e->api_dev + 256);
+  grec *dg = (grec *)((char *)e->api.p + 256);
   uint32_t *dout = (uint32_t *)(dg + n);
   HIPCHK(hipMemcpyAsync(dg, g.data(), sizeof(grec) * n, hipMemcpyHostToDevice, e->stream));
   k_api_msg_bytes<<<nblk(n, 256), 256, 0, e->stream>>>(e->d, dg, n, dout);
@@ -1674,56 +1653,46 @@ static int sorted_view(gx_engine *e, uint32_t view, uint32_t owner, bool by_name
   uint64_t *k0 = nullptr, *k1 = nullptr;
   gx_service *dout = nullptr;
   void *tmp = nullptr;
-  int rc = GX_OK;
   uint32_t n = 0;
-  auto fail = [&](hipError_t err) { return err == hipSuccess ? GX_OK : (err == hipErrorOutOfMemory ? GX_ENOMEM : GX_EIO); };
-#define VCK(x)                    \
-  do {                            \
-    rc = fail(x);                 \
-    if (rc) goto done;            \
-  } while (0)
-  VCK(hipMalloc(&cnt, sizeof(uint32_t) * (nb + 1)));
+  DevMem mem;  // this call's temporaries, freed on every return
+  GXTRY(mem.take(cnt, sizeof(uint32_t) * (nb + 1)));
   k_vc_count<<<nb, 256, 0, s>>>(d, vi, owner, cnt);
   k_vc_scan<<<1, 1024, 0, s>>>(cnt, nb);
-  VCK(hipMemcpyAsync(&n, &cnt[nb], sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-  VCK(hipStreamSynchronize(s));
+  HIPCHK(hipMemcpyAsync(&n, &cnt[nb], sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
   if (n) {
-    VCK(hipMalloc(&k0, sizeof(uint64_t) * n));
-    VCK(hipMalloc(&k1, sizeof(uint64_t) * n));
-    VCK(hipMalloc(&v0, sizeof(uint32_t) * n));
-    VCK(hipMalloc(&v1, sizeof(uint32_t) * n));
-    VCK(hipMalloc(&dout, sizeof(gx_service) * n));
+    GXTRY(mem.take(k0, sizeof(uint64_t) * n));
+    GXTRY(mem.take(k1, sizeof(uint64_t) * n));
+    GXTRY(mem.take(v0, sizeof(uint32_t) * n));
+    GXTRY(mem.take(v1, sizeof(uint32_t) * n));
+    GXTRY(mem.take(dout, sizeof(gx_service) * n));
     k_vc_write<<<nb, 256, 0, s>>>(d, vi, owner, cnt, k0, v0);
     size_t tb = 0, tb2 = 0;
-    if (gx_sort_u64_pairs(nullptr, &tb, k0, k1, v0, v1, n, 64 - GX_TS_SHIFT, s)) VCK(hipErrorUnknown);
+    if (gx_sort_u64_pairs(nullptr, &tb, k0, k1, v0, v1, n, 64 - GX_TS_SHIFT, s)) return GX_EIO;
     if (by_name) {
-      VCK(hipMalloc(&k32a, sizeof(uint32_t) * n));
-      VCK(hipMalloc(&k32b, sizeof(uint32_t) * n));
-      if (gx_sort_u32_pairs(nullptr, &tb2, k32a, k32b, v1, v0, n, 32, s)) VCK(hipErrorUnknown);
+      GXTRY(mem.take(k32a, sizeof(uint32_t) * n));
+      GXTRY(mem.take(k32b, sizeof(uint32_t) * n));
+      if (gx_sort_u32_pairs(nullptr, &tb2, k32a, k32b, v1, v0, n, 32, s)) return GX_EIO;
     }
-    VCK(hipMalloc(&tmp, std::max<size_t>(std::max(tb, tb2), 1)));
-    if (gx_sort_u64_pairs(tmp, &tb, k0, k1, v0, v1, n, 64 - GX_TS_SHIFT, s)) VCK(hipErrorUnknown);
+    GXTRY(mem.take(tmp, std::max<size_t>(std::max(tb, tb2), 1)));
+    if (gx_sort_u64_pairs(tmp, &tb, k0, k1, v0, v1, n, 64 - GX_TS_SHIFT, s)) return GX_EIO;
     uint32_t *order = v1;
     if (by_name) {
       k_vc_rank<<<nblk(n, 256), 256, 0, s>>>(e->name_rank, v1, k32a, n);
-      if (gx_sort_u32_pairs(tmp, &tb2, k32a, k32b, v1, v0, n, 32, s)) VCK(hipErrorUnknown);
+      if (gx_sort_u32_pairs(tmp, &tb2, k32a, k32b, v1, v0, n, 32, s)) return GX_EIO;
       order = v0;
     }
     k_vc_out<<<nblk(n, 256), 256, 0, s>>>(d, vi, order, n, dout);
     const uint32_t m = n < cap ? n : cap;
     if (m) {
-      VCK(hipMemcpyAsync(out, dout, sizeof(gx_service) * m, hipMemcpyDeviceToHost, s));
-      if (by_name && group_out) VCK(hipMemcpyAsync(group_out, k32b, sizeof(uint32_t) * m, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipMemcpyAsync(out, dout, sizeof(gx_service) * m, hipMemcpyDeviceToHost, s));
+      if (by_name && group_out) HIPCHK(hipMemcpyAsync(group_out, k32b, sizeof(uint32_t) * m, hipMemcpyDeviceToHost, s));
     }
-    VCK(hipStreamSynchronize(s));
-    VCK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipGetLastError());
   }
   if (n_out) *n_out = n;
-done:
-#undef VCK
-  for (void *p : {(void *)cnt, (void *)k0, (void *)k1, (void *)v0, (void *)v1, (void *)k32a, (void *)k32b, (void *)dout, tmp})
-    if (p) (void)hipFree(p);
-  return rc;
+  return GX_OK;
 }
 
 int gx_each_service_sorted(gx_engine *e, uint32_t view, uint32_t owner, gx_service *out, uint32_t cap,
@@ -1752,13 +1721,7 @@ int gx_set_service_names(gx_engine *e, const char *names, const uint64_t *off) {
     rank[idx[k]] = g;
   }
   HIPCHK(hipSetDevice(e->device));
-  if (!e->name_rank) {
-    if (hipMalloc(&e->name_rank, sizeof(uint32_t) * R) != hipSuccess) {
-      (void)hipGetLastError();
-      e->name_rank = nullptr;
-      return GX_ENOMEM;
-    }
-  }
+  if (!e->name_rank) GXTRY(e->mem.take(e->name_rank, sizeof(uint32_t) * R));
   HIPCHK(hipMemcpy(e->name_rank, rank.data(), sizeof(uint32_t) * R, hipMemcpyHostToDevice));
   return GX_OK;
 }
@@ -1811,23 +1774,20 @@ static int rebuild_logs(gx_engine *e) {
     cap = l.cap > cap ? l.cap : cap;
   }
   HIPCHK(hipStreamSynchronize(e->stream));
-  if (d.ev_log) (void)hipFree(d.ev_log);
-  if (d.ev_cnt) (void)hipFree(d.ev_cnt);
-  d.ev_log = nullptr;
-  d.ev_cnt = nullptr;
+  e->mem.drop(d.ev_log);
+  e->mem.drop(d.ev_cnt);
   d.ev_cap = 0;
   HIPCHK(hipMemset(d.ev_slot, 0xff, sizeof(int32_t) * d.Hl));
   e->log_views = views;
   if (views.empty()) return GX_OK;
-  if (hipMalloc((void **)&d.ev_log, sizeof(gx_change_event) * cap * views.size()) != hipSuccess ||
-      hipMalloc((void **)&d.ev_cnt, sizeof(uint32_t) * views.size()) != hipSuccess) {
-    (void)hipGetLastError();
+  int rc = e->mem.take(d.ev_log, sizeof(gx_change_event) * cap * views.size());
+  if (!rc) rc = e->mem.take(d.ev_cnt, sizeof(uint32_t) * views.size(), 0, e->stream);
+  if (rc) {
     e->listeners.clear();
     e->log_views.clear();
-    return GX_ENOMEM;
+    return rc;
   }
   d.ev_cap = cap;
-  HIPCHK(hipMemset(d.ev_cnt, 0, sizeof(uint32_t) * views.size()));
   for (size_t k = 0; k < views.size(); k++) {
     int32_t slot = (int32_t)k;
     HIPCHK(hipMemcpy(&d.ev_slot[views[k] - d.lo], &slot, sizeof(int32_t), hipMemcpyHostToDevice));
@@ -2166,8 +2126,8 @@ static int xplan_counts(gx_engine *e, const uint32_t **out) {
         hipEventCreateWithFlags(&e->xplan_ev[0], hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&e->xplan_ev[1], hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&e->xplan_join, hipEventDisableTiming) != hipSuccess ||
-        hipMalloc((void **)&e->xplan_dev, sizeof(uint32_t) * 2 * XPLAN_BATCH * d.G * d.G) != hipSuccess ||
-        hipHostMalloc((void **)&e->xplan_host, sizeof(uint32_t) * 2 * XPLAN_BATCH * d.G * d.G) != hipSuccess) {
+        hipHostMalloc((void **)&e->xplan_host, sizeof(uint32_t) * 2 * XPLAN_BATCH * d.G * d.G) != hipSuccess ||
+        e->mem.take(e->xplan_dev, sizeof(uint32_t) * 2 * XPLAN_BATCH * d.G * d.G)) {
       (void)hipGetLastError();
       return GX_ENOMEM;
     }
@@ -2583,7 +2543,7 @@ int gx_lock_census(gx_engine *e, uint32_t *unlocked) {
   int rc = ensure_api(e, sizeof(uint32_t));
   if (rc) return rc;
   set_round_fields(e);
-  uint32_t *dv = (uint32_t *)e->api_dev;
+  uint32_t *dv = (uint32_t *)e->api.p;
   HIPCHK(hipMemsetAsync(dv, 0, sizeof(uint32_t), e->stream));
   if (e->d.Hl) k_lock_census<<<nblk(e->d.Hl, 256), 256, 0, e->stream>>>(e->d, dv);
   return read_back(e, dv, unlocked);
@@ -2884,8 +2844,8 @@ int gx_fd_notify(gx_engine *e, uint32_t host, const gx_fd_msg *msgs, uint32_t n)
   int rc = ensure_api(e, sizeof(gx_fd_msg) * n);
   if (rc) return rc;
   set_round_fields(e);
-  HIPCHK(hipMemcpyAsync(e->api_dev, msgs, sizeof(gx_fd_msg) * n, hipMemcpyHostToDevice, e->stream));
-  k_fd_api_notify<<<1, 64, 0, e->stream>>>(e->d, host, (const gx_fd_msg *)e->api_dev, n);
+  HIPCHK(hipMemcpyAsync(e->api.p, msgs, sizeof(gx_fd_msg) * n, hipMemcpyHostToDevice, e->stream));
+  k_fd_api_notify<<<1, 64, 0, e->stream>>>(e->d, host, (const gx_fd_msg *)e->api.p, n);
   return sync_check(e);
 }
 
@@ -2895,8 +2855,8 @@ int gx_fd_get_broadcasts(gx_engine *e, uint32_t host, uint32_t limit, gx_fd_msg 
   int rc = ensure_api(e, 64 + sizeof(gx_fd_msg) * 64);
   if (rc) return rc;
   set_round_fields(e);
-  uint32_t *dn = (uint32_t *)e->api_dev;
-  gx_fd_msg *dm = (gx_fd_msg *)((char *)e->api_dev + 64);
+  uint32_t *dn = (uint32_t *)e->api.p;
+  gx_fd_msg *dm = (gx_fd_msg *)((char *)e->api.p + 64);
   k_fd_api_getb<<<1, 64, 0, e->stream>>>(e->d, host, limit, dm, dn);
   uint32_t n = 0;
   HIPCHK(hipMemcpyAsync(&n, dn, sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
@@ -2917,9 +2877,9 @@ int gx_fd_probe(gx_engine *e, uint32_t host, uint32_t *target, int *acked) {
   int rc = ensure_api(e, 64);
   if (rc) return rc;
   set_round_fields(e);
-  k_fd_api_probe<<<1, 64, 0, e->stream>>>(e->d, host, (uint32_t *)e->api_dev);
+  k_fd_api_probe<<<1, 64, 0, e->stream>>>(e->d, host, (uint32_t *)e->api.p);
   uint32_t x[2] = {0, 0};
-  HIPCHK(hipMemcpyAsync(x, e->api_dev, sizeof(x), hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipMemcpyAsync(x, e->api.p, sizeof(x), hipMemcpyDeviceToHost, e->stream));
   rc = sync_check(e);
   if (rc) return rc;
   if (target) *target = x[0];
@@ -2941,8 +2901,8 @@ int gx_fd_merge_state(gx_engine *e, uint32_t host, const uint64_t *remote) {
   int rc = ensure_api(e, sizeof(uint64_t) * e->d.H);
   if (rc) return rc;
   set_round_fields(e);
-  HIPCHK(hipMemcpyAsync(e->api_dev, remote, sizeof(uint64_t) * e->d.H, hipMemcpyHostToDevice, e->stream));
-  k_fd_api_merge_state<<<1, 64, 0, e->stream>>>(e->d, host, (const uint64_t *)e->api_dev);
+  HIPCHK(hipMemcpyAsync(e->api.p, remote, sizeof(uint64_t) * e->d.H, hipMemcpyHostToDevice, e->stream));
+  k_fd_api_merge_state<<<1, 64, 0, e->stream>>>(e->d, host, (const uint64_t *)e->api.p);
   return sync_check(e);
 }
 
