@@ -3,14 +3,11 @@
 off and GossipMessages is at most one message per target, 0 included. Round 4 once sent
 GossipMessages 0 down the size-gathered exchange and only a sync-debug GPU test noticed; these tests
 pin the choice on the CPU, for LocalShards and for DistShard over gloo."""
-import multiprocessing as mp
-import os
-import socket
-
 import pytest
 
 from sidecar_amd.abi import Engine, default_params
 from sidecar_amd.dist import LocalShards, planned_exchange
+from tests.ranks import run_ranks
 
 CASES = [  # (params, planned)
     (dict(gossip_messages=0), True),
@@ -50,45 +47,27 @@ def test_local_shards_take_the_planned_exchange(oracle_lib, kw, planned):
     assert sh.stats()["gossip_merges"] == whole.stats()["gossip_merges"]
 
 
-def _worker(rank, world, port, kw, q, chunk=None, rounds=6):
+def _worker(rank, world, kw, chunk=None, rounds=6):
     import torch.distributed as dist
     from sidecar_amd.dist import DistShard
     from tests.oracle_lib import load_oracle
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
     sh = DistShard(load_oracle(), rank, world, "cpu", **kw)
     if chunk:
         sh.CHUNK = chunk  # every per-peer segment in several all-to-all calls
     sh.run_rounds(rounds)
     st = sh.stats()
-    q.put((rank, dict(sh.exchange_paths), st["gossip_merges"], st, sh.e.digests()))
+    out = (rank, dict(sh.exchange_paths), st["gossip_merges"], st, sh.e.digests())
     dist.barrier()
     sh.close()
     dist.destroy_process_group()
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
+    return out
 
 
 @pytest.mark.parametrize("gm,planned", [(0, True), (1, True), (4, False)])
 def test_dist_shard_takes_the_planned_exchange(oracle_lib, gm, planned):
     kw = dict(BASE, gossip_messages=gm)
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    ps = [ctx.Process(target=_worker, args=(r, 2, port, kw, q)) for r in range(2)]
-    for p in ps:
-        p.start()
-    res = sorted([q.get(timeout=240) for _ in ps], key=lambda x: x[0])
-    for p in ps:
-        p.join(timeout=60)
-        assert p.exitcode == 0
+    res = run_ranks(_worker, 2, (kw,))
     want = {"planned": 6, "sized": 0} if planned else {"planned": 0, "sized": 6}
     assert all(r[1] == want for r in res), res
     whole = Engine(default_params(oracle_lib, **kw), lib=oracle_lib)
@@ -161,16 +140,7 @@ def test_dist_shard_planned_exchange_in_chunks(oracle_lib):
     packet slot (528 B) every gossip round is chunked, and the two gloo ranks end equal to the
     unsharded oracle (counters summed over the shards)."""
     kw = dict(BASE, gossip_messages=1, partition_end=0, n_hosts=48)
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    ps = [ctx.Process(target=_worker, args=(r, 2, port, kw, q, 200, 12)) for r in range(2)]
-    for p in ps:
-        p.start()
-    res = sorted([q.get(timeout=240) for _ in ps], key=lambda x: x[0])
-    for p in ps:
-        p.join(timeout=60)
-        assert p.exitcode == 0
+    res = run_ranks(_worker, 2, (kw, 200, 12))
     assert all(r[1] == {"planned": 12, "sized": 0} for r in res), res
     whole = Engine(default_params(oracle_lib, **kw), lib=oracle_lib)
     whole.run_rounds(12)

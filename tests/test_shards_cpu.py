@@ -2,16 +2,13 @@
 sidecar_amd/dist.py) must evolve bit-identically to the unsharded cluster — views, per-host
 bookkeeping, queue digests and the summed counters. Also over torch.distributed gloo with two
 processes (the same protocol the GPUs run over RCCL)."""
-import os
-import socket
-
 import numpy as np
 import pytest
-import torch.multiprocessing as mp
 
 from sidecar_amd.abi import Engine, default_params
 from sidecar_amd.dist import LocalShards
 from tests.parity import host_tuples
+from tests.ranks import run_ranks
 
 SCEN = {
     "storm": dict(n_hosts=48, n_services=8, init_mode=2, ae_period_rounds=10, partition_start=0,
@@ -85,28 +82,19 @@ def test_local_shards_match_whole(oracle_lib, name, G):
         assert_sharded_equal(whole, sh, f"{name} G={G} round {whole.round}")
 
 
-def _worker(rank, world, port, kw, rounds, q):
+def _worker(rank, world, kw, rounds):
     import torch.distributed as dist
     from sidecar_amd.dist import DistShard
     from tests.oracle_lib import load_oracle
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
     sh = DistShard(load_oracle(), rank, world, "cpu", **kw)
     sh.run_rounds(rounds)
     st = sh.stats()
     conv = sh.converged()
-    q.put((rank, sh.e.read_views(), host_tuples(sh.e), sh.e.digests(), st, conv, sh.ae_skipped))
+    out = (rank, sh.e.read_views(), host_tuples(sh.e), sh.e.digests(), st, conv, sh.ae_skipped)
     dist.barrier()
     dist.destroy_process_group()
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
+    return out
 
 
 LOCKED = dict(n_hosts=64, n_services=16, init_mode=2, ae_period_rounds=10, partition_start=0,
@@ -116,16 +104,7 @@ LOCKED = dict(n_hosts=64, n_services=16, init_mode=2, ae_period_rounds=10, parti
 @pytest.mark.parametrize("name", ["storm", "churn_odd", "locked"])
 def test_gloo_world2_matches_whole(oracle_lib, name):
     kw, rounds, world = (LOCKED if name == "locked" else SCEN[name]), 45, 2
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    ps = [ctx.Process(target=_worker, args=(r, world, port, kw, rounds, q)) for r in range(world)]
-    for p in ps:
-        p.start()
-    res = sorted([q.get(timeout=240) for _ in ps], key=lambda x: x[0])
-    for p in ps:
-        p.join(timeout=60)
-        assert p.exitcode == 0
+    res = run_ranks(_worker, world, (kw, rounds))
     whole = Engine(default_params(oracle_lib, **kw), lib=oracle_lib)
     whole.run_rounds(rounds)
     assert np.array_equal(np.concatenate([r[1] for r in res]), whole.read_views())
