@@ -230,7 +230,12 @@ typedef struct gx_params {
    * config/config.go:45). GX_PP_MATCHING: a seeded perfect matching, every host in one exchange.
    * GX_PP_INITIATE: every live host initiates one exchange with a peer drawn at random, so a host
    * takes part in 1 + (number of initiators that drew it) exchanges, as with memberlist's
-   * per-node timers. Both sides of an exchange merge the other's round-start state. */
+   * per-node timers. The exchanges run in initiator order; both sides of an exchange merge the
+   * other's state as it was before that exchange. Exchanges with no host in common commute, so they
+   * run in batches: an exchange goes into the batch after the last one that holds either of its
+   * hosts. The list and its batches follow from (seed, round) alone. Not with fd_enable
+   * (GX_EINVAL); sharded engines of the HIP engine run a batch per pass of the push-pull calls (the
+   * sharded rounds below), the CPU oracle runs it unsharded only. */
   uint32_t push_pull_mode;
   /* Engine bound (no reference counterpart): inbox slots per receiver, 1..256 (0 = 64, or 256 with
    * gossip_messages > 1). A receiver with more packets in a round takes the serial overflow path;
@@ -550,6 +555,17 @@ int gx_round_merge(gx_engine *e); /* phase 4: gather-then-merge of local + recei
  * [gx_ae_merge_local] -> exchange -> gx_ae_delta_bytes (received digests) -> gx_ae_delta_pack
  * (lead blocks) -> exchange -> gx_ae_return_bytes (received lead blocks) -> gx_ae_return_pack ->
  * exchange -> gx_ae_merge (both inboxes).
+ * With GX_PP_INITIATE (HIP engine) a push-pull round is that chain once per batch of the round's
+ * exchanges, in batch order: gx_ae_bytes plans the batch at the engine's cursor (its pairs
+ * bucketed by the partner's shard exactly like the matching's; `pair index` in the messages is the
+ * exchange's place in the round's list, initiator order, which both sides derive), the digests are
+ * taken then, so a batch sees the rows as the batch before left them, gx_ae_merge joins the
+ * shard-local pairs and moves the cursor on, gx_round_end puts it back. Past the last batch the
+ * calls report zero bytes and do nothing, as in a round without push-pull. Every shard makes the
+ * same number of passes: the product exports the symbol gx_ae_batches(e, uint32_t *n), outside this
+ * header's declarations like its diagnostics (the oracle has no such symbol): *n = 0 when the
+ * round has no push-pull or nobody initiates, 1 for the matching, the batch count with
+ * GX_PP_INITIATE; computed on the host from (seed, round), no device wait, equal on every shard.
  * Digest of block b = slots [b*512, min(R, (b+1)*512)) of a row, i = slot index in the row,
  * w = slot word, sums mod 2^64, L = literal count of the block's lead encoding, u32 arithmetic
  * mod 2^32 in h: x = w ^ (i << 40) ^ i, lo/hi = its halves, a = (lo ^ rotl32(hi, 16)) * 0x85EBCA6B,
@@ -574,8 +590,10 @@ int gx_round_end(gx_engine *e);   /* round += 1, wake due sleepers */
  * hold the lock this round (a synchronizing call). When the sum over every shard is 0 at a
  * push-pull round, every pair fails, and gx_ae_skip_locked stands for the whole exchange
  * (gx_ae_bytes .. gx_ae_merge; then gx_round_end): the same counts (ae_locked once per pair, by
- * the shard of its first host; first_locked_round), nothing moved. GX_EINVAL if a host here is
- * free, for an unsharded engine (G = 1), or with the failure detector or departures. */
+ * the shard of its first host; first_locked_round), nothing moved. With GX_PP_INITIATE it stands
+ * for every batch of the round: ae_locked once per exchange, by its initiator's shard. GX_EINVAL
+ * if a host here is free, for an unsharded engine (G = 1), or with the failure detector or
+ * departures. */
 int gx_lock_census(gx_engine *e, uint32_t *unlocked);
 int gx_ae_skip_locked(gx_engine *e);
 /* A planned gossip round in two calls (fewer host calls per round for an exchange layer; the same

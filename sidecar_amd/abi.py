@@ -33,6 +33,7 @@ LOCK_PENDING_EXPIRE, LOCK_DEFER_MERGE, LOCK_BUF_SHIFT = 4, 8, 8  # gx_host_state
 # gx_params.lock_readers (gx.h): the waiting merges' pool is direct-mapped (slot v % lock_defer_slots)
 # or claimed from a free list (HIP engine only)
 LOCK_READERS_OFF, LOCK_READERS_MAPPED, LOCK_READERS_CLAIMED = 0, 1, 2
+PP_MATCHING, PP_INITIATE = 0, 1  # gx_params.push_pull_mode (gx.h)
 
 K_NAMES = ["owner", "scan", "storm", "send", "route", "merge", "ae", "converge", "encode", "decode", "fd"]
 
@@ -840,7 +841,17 @@ class Engine:
     def is_ae_round(self) -> bool:
         """This round is a push-pull round (every shard agrees: the schedule is global)."""
         p = self.params
+        if p.ae_period_rounds and p.push_pull_stagger:
+            return True  # some host's staggered timer, every round
         return bool(p.ae_period_rounds) and self.round % p.ae_period_rounds == p.ae_phase
+
+    def ae_batches(self) -> int:
+        """Runs of the push-pull chain (ae_bytes .. ae_merge) this round takes on a sharded engine: 0
+        without push-pull or initiators, 1 for the matching, the batch count in GX_PP_INITIATE. A
+        symbol of the HIP engine, not in gx.h's declarations; host-only, the same on every shard."""
+        n = C.c_uint32(0)
+        check(self.lib.gx_ae_batches(self.h, C.byref(n)), "gx_ae_batches")
+        return int(n.value)
 
     def set_stream(self, stream_ptr, async_phases: bool):
         """Run this engine's device work on the caller's HIP stream (0 = the default stream; None =

@@ -31,6 +31,7 @@
 #include <algorithm>
 #include <chrono>
 #include <deque>
+#include <numeric>
 #include <string>
 #include <thread>
 #include <type_traits>
@@ -177,7 +178,12 @@ struct gx_engine {
   int device;
   int timing;
   std::vector<TimedLaunch> pending_ev;
-  std::vector<uint32_t> pp_host;  // GX_PP_INITIATE: this round's exchanges, batch by batch (a then b)
+  // GX_PP_INITIATE, the schedule of round pp_round (pp_schedule): the exchanges batch by batch
+  // (pp_host: the n initiators, then the n partners), each one's index in initiator order, batch q =
+  // [pp_off[q], pp_off[q + 1]); a sharded engine runs the batch at pp_cursor (gx_ae_bytes .. gx_ae_merge)
+  std::vector<uint32_t> pp_host, pp_idx, pp_off;
+  int64_t pp_round = -1;
+  uint32_t pp_cursor;
   uint32_t *pp_dev;
   int32_t *pp_prow;               // all -1: every exchange is local
   uint32_t *name_rank;            // [R] ByService: rank of each record's Service.Name (gx_set_service_names)
@@ -214,8 +220,9 @@ struct gx_engine {
   std::vector<uint32_t> pack_gstart;  // pack index range per destination shard
   std::vector<uint64_t> delta_off_h;
   uint64_t delta_total, lead_in_total, ret_total;
-  int ae_delta_round = -1, ae_ret_round = -1;
-  int ae_planned_round = -1;
+  // the chain's guards: the step (ae_step: round and batch) each call last completed for
+  int64_t ae_delta_round = -1, ae_ret_round = -1;
+  int64_t ae_planned_round = -1;
   int64_t ae_local_round = -1;
   // listeners: host-side channels fed from the per-view device event logs
   struct Listener {
@@ -748,11 +755,12 @@ static bool pp_initiates(const Dev &d, uint32_t i) {
   return (uint64_t)d.round % d.p.ae_period_rounds == rng4(d.p.seed, ST_PP_PHASE, i, 0, 0) % d.p.ae_period_rounds;
 }
 
-// GX_PP_INITIATE (unsharded engines): every live host starts one exchange with a partner drawn
-// at random on its side; the exchanges run in initiator order, in batches of exchanges with no
-// host in common (an exchange goes into the batch after the last one holding either of its hosts).
-// The oracle's pp_batches computes the same batches; each batch is one k_ae_plan launch over its
-// pair list (local pairs: both sides merge the other's pre-exchange row).
+// GX_PP_INITIATE: every live host starts one exchange with a partner drawn at random on its side;
+// the exchanges run in initiator order, in batches of exchanges with no host in common (an exchange
+// goes into the batch after the last one holding either of its hosts). The oracle's pp_batches
+// computes the same batches (pp_schedule). On an unsharded engine each batch is one k_ae_plan
+// launch over its pair list (local pairs: both sides merge the other's pre-exchange row); on a
+// sharded one each batch is one run of the push-pull chain over its pairs (ae_plan).
 static bool ae_partner(const Dev &d, uint32_t i, uint32_t *out) {
   uint32_t base = 0, m = d.H;
   if (d.partitioned && !d.p.fd_enable) {
@@ -785,8 +793,12 @@ static void launch_ae_plan(gx_engine *e, bool pf2, unsigned np, hipStream_t st, 
     (ev ? k_ae_plan_ev<V()> : pf2 ? k_ae_plan_pf2<V()> : k_ae_plan<V()>)<<<np, 256, 0, st>>>(e->d, pa, pb, prow, pcount, in, skip);
   });
 }
-static int ae_initiate(gx_engine *e) {
+// This round's exchanges and batches (the oracle's pp_batches), from (seed, round) alone: every
+// shard computes the same schedule. Kept for the round (pp_round); returns the batch count.
+static uint32_t pp_schedule(gx_engine *e) {
   Dev &d = e->d;
+  if (e->pp_round == d.round) return (uint32_t)e->pp_off.size() - 1;
+  set_round_fields(e);  // ae_partner draws inside a partition's side
   const bool dep = d.departures;
   std::vector<uint32_t> last(d.H, 0), bat, ia, ib;
   uint32_t nb = 0;
@@ -803,17 +815,41 @@ static int ae_initiate(gx_engine *e) {
     nb = std::max(nb, k);
   }
   const size_t n = ia.size();
-  if (!n) return GX_OK;
-  std::vector<uint32_t> off(nb + 1, 0);
-  for (uint32_t x : bat) off[x + 1]++;
-  for (uint32_t q = 0; q < nb; q++) off[q + 1] += off[q];
-  std::vector<uint32_t> cur(off.begin(), off.end() - 1);
+  e->pp_off.assign(nb + 1, 0);
+  for (uint32_t x : bat) e->pp_off[x + 1]++;
+  for (uint32_t q = 0; q < nb; q++) e->pp_off[q + 1] += e->pp_off[q];
+  std::vector<uint32_t> cur(e->pp_off.begin(), e->pp_off.end() - 1);
   e->pp_host.assign(2 * n, 0);
+  e->pp_idx.assign(n, 0);
   for (size_t t = 0; t < n; t++) {  // stable: initiator order inside a batch
     const uint32_t at = cur[bat[t]]++;
     e->pp_host[at] = ia[t];
     e->pp_host[n + at] = ib[t];
+    e->pp_idx[at] = (uint32_t)t;
   }
+  e->pp_round = d.round;
+  e->pp_cursor = 0;
+  return nb;
+}
+// A sharded engine's push-pull chain (gx_ae_bytes .. gx_ae_merge) has a step to run: the round's
+// matching, or in GX_PP_INITIATE the batch at the cursor (past the last one the calls do nothing,
+// as on a round without push-pull) ...
+static bool ae_step_due(gx_engine *e) {
+  if (e->d.G < 2 || !ae_round(e)) return false;
+  if (e->d.p.push_pull_mode != GX_PP_INITIATE) return true;
+  const uint32_t nb = pp_schedule(e);
+  return e->pp_cursor < nb;
+}
+// ... and its name for the chain's guards: the round and the batch (a batch count is at most H)
+static int64_t ae_step(const gx_engine *e) {
+  return e->d.round * (2 * (int64_t)GX_MAX_HOSTS) + (e->d.p.push_pull_mode == GX_PP_INITIATE ? e->pp_cursor : 0);
+}
+static int ae_initiate(gx_engine *e) {
+  Dev &d = e->d;
+  const uint32_t nb = pp_schedule(e);
+  const size_t n = e->pp_idx.size();
+  if (!n) return GX_OK;
+  const std::vector<uint32_t> &off = e->pp_off;
   HIPCHK(hipMemcpyAsync(e->pp_dev, e->pp_host.data(), sizeof(uint32_t) * 2 * n, hipMemcpyHostToDevice, e->stream));
   AeIn none;
   memset(&none, 0, sizeof(none));
@@ -1010,8 +1046,7 @@ static int check_params(const gx_params *p) {
   if (p->n_shards > 1 && (p->shard_id >= p->n_shards || p->n_shards > p->n_hosts || p->n_shards > 64)) return GX_EINVAL;
   if (p->depart_ppm > 1000000u) return GX_EINVAL;
   if (p->gossip_messages > 16) return GX_EINVAL;
-  if (p->push_pull_mode > GX_PP_INITIATE || (p->push_pull_mode == GX_PP_INITIATE && (p->n_shards > 1 || p->fd_enable)))
-    return GX_EINVAL;
+  if (p->push_pull_mode > GX_PP_INITIATE || (p->push_pull_mode == GX_PP_INITIATE && p->fd_enable)) return GX_EINVAL;
   if (p->inbox_slots > GX_DI_MAX) return GX_EINVAL;
   if (p->lock_model > 1 || p->lock_buffer < 1 || p->lock_buffer > 65535) return GX_EINVAL;
   if (p->lock_model && (((uint64_t)p->n_hosts + (p->n_shards > 1 ? p->n_shards : 1) - 1) / (p->n_shards > 1 ? p->n_shards : 1)) *
@@ -1164,7 +1199,7 @@ static int create_buffers(gx_engine *e) {
   TAKE(d.work_cnt, sizeof(uint32_t) * GX_WC_N, 0, s);
   TAKE(d.quiet_w, sizeof(uint32_t) * 2 * d.QW, 0, s);  // (0: no round is quiet)
   TAKE(d.work, sizeof(uint32_t) * H);
-  if (p->push_pull_mode == GX_PP_INITIATE) {
+  if (p->push_pull_mode == GX_PP_INITIATE && d.G < 2) {  // a sharded engine's batches go through ae_pa, ae_pb
     TAKE(e->pp_dev, sizeof(uint32_t) * 2 * Hg);
     TAKE(e->pp_prow, sizeof(int32_t) * Hg, 0xff, s);
   }
@@ -1289,6 +1324,7 @@ int gx_set_round(gx_engine *e, int64_t round) {
     HIPCHK(hipMemsetAsync(e->d.work_cnt, 0, sizeof(uint32_t) * GX_WC_ERR, e->stream));
   }
   e->d.round = round;
+  e->pp_cursor = 0;
   quiet_invalidate(e);
   set_round_fields(e);
   int rc = wake_all(e);
@@ -2214,30 +2250,44 @@ int gx_round_merge(gx_engine *e) {
 static int ae_plan(gx_engine *e, uint64_t *bytes) {
   Dev &d = e->d;
   set_round_fields(e);
-  std::vector<uint32_t> pa, pb;
-  uint32_t groups[2][2];
-  int ng;
-  if (d.pair_split) {
-    groups[0][0] = 0; groups[0][1] = d.H / 2;
-    groups[1][0] = d.H / 2; groups[1][1] = d.H - d.H / 2;
-    ng = 2;
-  } else {
-    groups[0][0] = 0; groups[0][1] = d.H;
-    ng = 1;
-  }
-  // the pair schedule (Feistel permutations, as k_ae draws it) on the device, read back once
-  uint32_t n0 = groups[0][1] / 2, n1 = ng > 1 ? groups[1][1] / 2 : 0, np = n0 + n1;
-  uint64_t key0 = rng4(d.p.seed, ST_AE, (uint64_t)d.round, groups[0][0], 0);
-  uint64_t key1 = ng > 1 ? rng4(d.p.seed, ST_AE, (uint64_t)d.round, groups[1][0], 0) : 0;
-  pa.resize(np);
-  pb.resize(np);
-  if (np) {
-    k_ae_pairs<<<(np + 255) / 256, 256, 0, e->stream>>>(groups[0][0], groups[0][1], key0, groups[1][0],
-                                                         ng > 1 ? groups[1][1] : 0, key1, n0, np, e->ae_pa, e->ae_pb);
-    HIPCHK(hipMemcpyAsync(pa.data(), e->ae_pa, 4ull * np, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipMemcpyAsync(pb.data(), e->ae_pb, 4ull * np, hipMemcpyDeviceToHost, e->stream));
-    int rc = sync_check(e);
+  std::vector<uint32_t> pa, pb, pt;  // pt: each pair's index in the round's list (the messages' pair index)
+  if (d.p.push_pull_mode == GX_PP_INITIATE) {
+    // the batch at the cursor (ae_step_due): its exchanges, named by their place in initiator order
+    pp_schedule(e);
+    const size_t n = e->pp_idx.size(), lo = e->pp_off[e->pp_cursor], hi = e->pp_off[e->pp_cursor + 1];
+    if (hi - lo > d.H / 2) return GX_EINVAL;  // hosts of a batch are disjoint: the pair buffers hold H / 2 + 1
+    pa.assign(e->pp_host.begin() + lo, e->pp_host.begin() + hi);
+    pb.assign(e->pp_host.begin() + n + lo, e->pp_host.begin() + n + hi);
+    pt.assign(e->pp_idx.begin() + lo, e->pp_idx.begin() + hi);
+    int rc = sync_check(e);  // the batch before (its launches read the plan rewritten below) is done
     if (rc) return rc;
+  } else {
+    uint32_t groups[2][2];
+    int ng;
+    if (d.pair_split) {
+      groups[0][0] = 0; groups[0][1] = d.H / 2;
+      groups[1][0] = d.H / 2; groups[1][1] = d.H - d.H / 2;
+      ng = 2;
+    } else {
+      groups[0][0] = 0; groups[0][1] = d.H;
+      ng = 1;
+    }
+    // the pair schedule (Feistel permutations, as k_ae draws it) on the device, read back once
+    uint32_t n0 = groups[0][1] / 2, n1 = ng > 1 ? groups[1][1] / 2 : 0, np = n0 + n1;
+    uint64_t key0 = rng4(d.p.seed, ST_AE, (uint64_t)d.round, groups[0][0], 0);
+    uint64_t key1 = ng > 1 ? rng4(d.p.seed, ST_AE, (uint64_t)d.round, groups[1][0], 0) : 0;
+    pa.resize(np);
+    pb.resize(np);
+    pt.resize(np);
+    std::iota(pt.begin(), pt.end(), 0u);
+    if (np) {
+      k_ae_pairs<<<(np + 255) / 256, 256, 0, e->stream>>>(groups[0][0], groups[0][1], key0, groups[1][0],
+                                                           ng > 1 ? groups[1][1] : 0, key1, n0, np, e->ae_pa, e->ae_pb);
+      HIPCHK(hipMemcpyAsync(pa.data(), e->ae_pa, 4ull * np, hipMemcpyDeviceToHost, e->stream));
+      HIPCHK(hipMemcpyAsync(pb.data(), e->ae_pb, 4ull * np, hipMemcpyDeviceToHost, e->stream));
+      int rc = sync_check(e);
+      if (rc) return rc;
+    }
   }
   // a pair with a crashed member does not run (both shards skip it alike; pair indices unchanged)
   std::vector<uint8_t> runs(pa.size(), 1);
@@ -2268,7 +2318,7 @@ static int ae_plan(gx_engine *e, uint64_t *bytes) {
       bool la = own(e, pa[t]);
       uint32_t mine = la ? pa[t] : pb[t], other = la ? pb[t] : pa[t];
       pack_host.push_back(mine);
-      pack_t.push_back(t);
+      pack_t.push_back(pt[t]);
       pack_other.push_back(other);
       pack_first.push_back(la ? 1 : 0);
       bytes[g] += dig_bytes(e);
@@ -2302,7 +2352,7 @@ static int ae_plan(gx_engine *e, uint64_t *bytes) {
     HIPCHK(hipMemsetAsync(e->ae_skip, 0, e->n_pack, e->stream));
   }
   if (pp_state(d)) k_fd_snap<<<2048, 256, 0, e->stream>>>(d);  // round-start member lists (pushPull)
-  e->ae_planned_round = (int)d.round;
+  e->ae_planned_round = ae_step(e);
   return GX_OK;
 }
 
@@ -2312,14 +2362,14 @@ int gx_ae_bytes(gx_engine *e, uint64_t *bytes) {
   for (uint32_t g = 0; g < e->d.G; g++) bytes[g] = 0;
   e->n_plan = e->n_pack = e->n_plan_rows = 0;
   e->ae_planned_round = -1;
-  if (e->d.G < 2 || !ae_round(e)) return GX_OK;
+  if (!ae_step_due(e)) return GX_OK;
   return ae_plan(e, bytes);
 }
 
 int gx_ae_pack(gx_engine *e, void *buf, uint64_t cap) {
   if (!e || (cap && !buf)) return GX_EINVAL;
   if (!e->n_pack) return GX_OK;
-  if (e->ae_planned_round != (int)e->d.round || cap < e->n_pack * dig_bytes(e)) return GX_EINVAL;
+  if (e->ae_planned_round != ae_step(e) || cap < e->n_pack * dig_bytes(e)) return GX_EINVAL;
   HIPCHK(hipSetDevice(e->device));
   with_flag(vec_of(e), [&](auto V) {
     k_ae_digest<V()><<<e->n_pack, 256, 0, e->stream>>>(e->d, e->ae_pack_host, e->ae_pack_t, e->ae_pack_other,
@@ -2337,8 +2387,8 @@ int gx_ae_delta_bytes(gx_engine *e, const void *digests, uint64_t bytes, uint64_
   for (uint32_t g = 0; g < d.G; g++) out[g] = 0;
   e->ae_delta_round = e->ae_ret_round = -1;
   e->delta_total = e->lead_in_total = 0;
-  if (d.G < 2 || !ae_round(e)) return bytes ? GX_EINVAL : GX_OK;
-  if (e->ae_planned_round != (int)d.round || bytes != e->n_pack * dig_bytes(e)) return GX_EINVAL;
+  if (!ae_step_due(e)) return bytes ? GX_EINVAL : GX_OK;
+  if (e->ae_planned_round != ae_step(e) || bytes != e->n_pack * dig_bytes(e)) return GX_EINVAL;
   const uint32_t np = e->n_pack;
   std::vector<uint64_t> sz(2 * (size_t)np);
   if (np) {
@@ -2369,14 +2419,14 @@ int gx_ae_delta_bytes(gx_engine *e, const void *digests, uint64_t bytes, uint64_
   e->delta_total = o;
   e->lead_in_total = oi;
   if (np) HIPCHK(hipMemcpy(e->ae_off, e->delta_off_h.data(), sizeof(uint64_t) * 2 * np, hipMemcpyHostToDevice));
-  e->ae_delta_round = (int)d.round;
+  e->ae_delta_round = ae_step(e);
   return GX_OK;
 }
 
 int gx_ae_delta_pack(gx_engine *e, void *buf, uint64_t cap) {
   if (!e || (cap && !buf)) return GX_EINVAL;
   if (!e->n_pack) return GX_OK;
-  if (e->ae_delta_round != (int)e->d.round || cap < e->delta_total) return GX_EINVAL;
+  if (e->ae_delta_round != ae_step(e) || cap < e->delta_total) return GX_EINVAL;
   HIPCHK(hipSetDevice(e->device));
   if (ae_wave_blocks(e))
     k_ae_lead_pack_w<<<e->n_pack, 256, 0, e->stream>>>(e->d, e->ae_pack_host, e->ae_pack_t, e->ae_mask, e->ae_cnt,
@@ -2398,8 +2448,8 @@ int gx_ae_return_bytes(gx_engine *e, const void *lead, uint64_t lead_bytes, uint
   e->ae_ret_round = -1;
   e->ret_total = 0;
   const uint32_t np = e->n_pack;
-  if (d.G < 2 || !ae_round(e) || !np) return lead_bytes ? GX_EINVAL : GX_OK;
-  if (e->ae_delta_round != (int)d.round || lead_bytes != e->lead_in_total) return GX_EINVAL;
+  if (!ae_step_due(e) || !np) return lead_bytes ? GX_EINVAL : GX_OK;
+  if (e->ae_delta_round != ae_step(e) || lead_bytes != e->lead_in_total) return GX_EINVAL;
   if (ae_wave_blocks(e))
     k_ae_ret_w<true><<<np, 256, 0, e->stream>>>(d, e->ae_pack_host, e->ae_pack_t, e->ae_fmask, e->ae_nfol, e->ae_lt,
                                                 (const uint8_t *)lead, e->ae_off + np, e->nblk, e->nmw,
@@ -2427,7 +2477,7 @@ int gx_ae_return_bytes(gx_engine *e, const void *lead, uint64_t lead_bytes, uint
   }
   e->ret_total = o;
   HIPCHK(hipMemcpy(e->ae_off + 2 * np, off.data(), sizeof(uint64_t) * 2 * np, hipMemcpyHostToDevice));
-  e->ae_ret_round = (int)d.round;
+  e->ae_ret_round = ae_step(e);
   return GX_OK;
 }
 
@@ -2435,7 +2485,7 @@ int gx_ae_return_pack(gx_engine *e, const void *lead, uint64_t lead_bytes, void 
   if (!e || (cap && !buf) || (lead_bytes && !lead)) return GX_EINVAL;
   const uint32_t np = e->n_pack;
   if (!np) return GX_OK;
-  if (e->ae_ret_round != (int)e->d.round || cap < e->ret_total || lead_bytes != e->lead_in_total) return GX_EINVAL;
+  if (e->ae_ret_round != ae_step(e) || cap < e->ret_total || lead_bytes != e->lead_in_total) return GX_EINVAL;
   HIPCHK(hipSetDevice(e->device));
   if (ae_wave_blocks(e))
     k_ae_ret_w<false><<<np, 256, 0, e->stream>>>(e->d, e->ae_pack_host, e->ae_pack_t, e->ae_fmask, e->ae_nfol,
@@ -2479,8 +2529,8 @@ static void ae_plan_launch(gx_engine *e, uint32_t lo, uint32_t hi, const void *l
 int gx_ae_merge_local(gx_engine *e) {
   if (!e) return GX_EINVAL;
   HIPCHK(hipSetDevice(e->device));
-  if (!ae_round(e) || e->d.G < 2 || e->ae_local_round == e->d.round) return GX_OK;
-  if (e->ae_planned_round != (int)e->d.round) return GX_EINVAL;
+  if (!ae_step_due(e) || e->ae_local_round == ae_step(e)) return GX_OK;
+  if (e->ae_planned_round != ae_step(e)) return GX_EINVAL;
   // on the side stream, after the rows are packed: the exchange layer's collectives (ordered
   // behind `stream`) run while these merges do; gx_ae_merge joins them back
   HIPCHK(hipEventRecord(e->side_start, e->stream));
@@ -2489,7 +2539,7 @@ int gx_ae_merge_local(gx_engine *e) {
   HIPCHK(hipEventRecord(e->side_done, e->side_stream));
   e->side_pending = true;
   HIPCHK(hipGetLastError());
-  e->ae_local_round = e->d.round;
+  e->ae_local_round = ae_step(e);
   return GX_OK;
 }
 
@@ -2502,10 +2552,11 @@ int gx_ae_merge(gx_engine *e, const void *lead, uint64_t lead_bytes, const void 
     int rc = ae_whole_impl(e, false);
     return rc ? rc : sync_check(e);
   }
-  if (e->ae_planned_round != (int)e->d.round) return GX_EINVAL;
+  if (!ae_step_due(e)) return (lead_bytes || ret_bytes) ? GX_EINVAL : GX_OK;  // past the round's last batch
+  if (e->ae_planned_round != ae_step(e)) return GX_EINVAL;
   const uint32_t np = e->n_pack;
   if (np) {
-    if (e->ae_ret_round != (int)e->d.round || lead_bytes != e->lead_in_total) return GX_EINVAL;
+    if (e->ae_ret_round != ae_step(e) || lead_bytes != e->lead_in_total) return GX_EINVAL;
     // the return inbox: per source shard a size table, then that shard's messages
     std::vector<uint64_t> rio(np), tab;
     uint64_t o = 0;
@@ -2525,15 +2576,16 @@ int gx_ae_merge(gx_engine *e, const void *lead, uint64_t lead_bytes, const void 
     if (o != ret_bytes) return GX_EINVAL;
     HIPCHK(hipMemcpy(e->ae_rioff, rio.data(), sizeof(uint64_t) * np, hipMemcpyHostToDevice));
   }
-  bool local_done = e->ae_local_round == e->d.round;
+  bool local_done = e->ae_local_round == ae_step(e);
   ae_plan_launch(e, 0, local_done ? e->n_plan_rows : e->n_plan, lead, ret);
   if (pp_state(e->d) && e->n_plan) {  // pushPull's membership half, every planned pair
     LaunchTimer t(e, GX_K_FD);
     k_fd_pushpull_plan<<<2 * e->n_plan, 64, 0, e->stream>>>(e->d, e->ae_pa, e->ae_pb, e->ae_prow, e->ae_skip,
                                                              e->fd_rsnap);
   }
-  int jr = join_side(e);  // the next round's phases see the local pairs merged
+  int jr = join_side(e);  // the next batch, and the next round's phases, see the local pairs merged
   if (jr) return jr;
+  if (e->d.p.push_pull_mode == GX_PP_INITIATE) e->pp_cursor++;  // the chain's next run takes the next batch
   return phase_done(e);
 }
 
@@ -2563,6 +2615,20 @@ int gx_ae_skip_locked(gx_engine *e) {
   if (rc) return rc;
   if (unlocked) return GX_EINVAL;  // a host here is free: the pairs must run the exchange
   set_round_fields(e);
+  if (d.p.push_pull_mode == GX_PP_INITIATE) {  // once per exchange, by its initiator's shard (pp_schedule)
+    const uint32_t nb = pp_schedule(e);
+    const size_t n = e->pp_idx.size();
+    uint32_t n_first = 0, any = 0;
+    for (size_t t = 0; t < n; t++) {
+      const bool la = own(e, e->pp_host[t]), lb = own(e, e->pp_host[n + t]);
+      n_first += la ? 1u : 0u;
+      any |= (la || lb) ? 1u : 0u;
+    }
+    e->pp_cursor = nb;  // no batch is left to run
+    if (!n) return GX_OK;
+    k_ae_locked_note<<<1, 64, 0, e->stream>>>(d, n_first, any);
+    return phase_done(e);
+  }
   uint32_t base[2] = {0, d.H / 2}, len[2] = {d.H, 0};
   int ng = 1;
   if (d.pair_split) {
@@ -2598,6 +2664,7 @@ int gx_round_end(gx_engine *e) {
   int rc = join_side(e);
   if (rc) return rc;
   e->d.round++;
+  e->pp_cursor = 0;
   rc = wake_all(e);
   return rc ? rc : phase_done(e);
 }
@@ -2927,6 +2994,16 @@ int gx_xplan_waits(gx_engine *e, uint64_t *out) {
   if (!e || !out) return GX_EINVAL;
   out[0] = e->xplan_waits[0];
   out[1] = e->xplan_waits[1];
+  return GX_OK;
+}
+
+// Outside gx.h's declarations (described there with the sharded rounds): how many runs of the
+// push-pull chain gx_ae_bytes .. gx_ae_merge this round takes on a sharded engine: 0 when it is not
+// a push-pull round or nobody initiates, 1 for the matching, the batch count in GX_PP_INITIATE.
+// From (seed, round) on the host: no device work, the same answer on every shard.
+int gx_ae_batches(gx_engine *e, uint32_t *n) {
+  if (!e || !n) return GX_EINVAL;
+  *n = !ae_round(e) ? 0 : e->d.p.push_pull_mode == GX_PP_INITIATE ? pp_schedule(e) : 1;
   return GX_OK;
 }
 

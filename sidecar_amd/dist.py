@@ -21,7 +21,7 @@ from typing import List
 import numpy as np
 import torch
 
-from .abi import Engine, GxParams, default_params
+from .abi import PP_INITIATE, Engine, GxParams, default_params
 
 # stats that hold the earliest round something happened (-1: never): the minimum over shards
 FIRST_ROUND_STATS = ("first_drop_round", "first_locked_round")
@@ -121,6 +121,7 @@ class ShardRounds:
         self.ae_trace = []
         self.ae_skipped = 0  # push-pull rounds with every host locked (gx_ae_skip_locked)
         self.skip_locked = True  # False: run the whole exchange even then (wire tests)
+        self.ae_batches_run = 0  # GX_PP_INITIATE: runs of the push-pull chain, one per batch
         self._pb = None
 
     @property
@@ -178,30 +179,47 @@ class ShardRounds:
             s.e.round_merge()
         return self.shards[0].e.is_ae_round()  # every shard agrees: the schedule is global
 
-    def _push_pull(self):
-        """The push-pull steps of a round and its end: digests, the blocks each side leads, the
-        partners' return blocks (gx.h); shard-local pairs overlap the exchanges. With every host of
-        the cluster locked (one census reduction) every pair fails: the counts only."""
+    def _ae_chain(self):
+        """One run of the push-pull chain over the pairs the engines plan (the round's matching, or
+        one batch of GX_PP_INITIATE): digests, the blocks each side leads, the partners' return
+        blocks (gx.h); shard-local pairs overlap the exchanges."""
         es = self.engines
-        if self.G > 1 and self.skip_locked and lock_shortcut(es[0].params) and \
+        dsz, dig = self._exchange_sized([e.ae_bytes() for e in es], lambda i, p, c: es[i].ae_pack(p, c),
+                                        after_pack=lambda e: e.ae_merge_local())
+        lsz, lead = self._exchange_sized([e.ae_delta_bytes(_ptr(x), x.numel()) for e, x in zip(es, dig)],
+                                         lambda i, p, c: es[i].ae_delta_pack(p, c))
+        rsz, ret = self._exchange_sized(
+            [e.ae_return_bytes(_ptr(x), x.numel()) for e, x in zip(es, lead)],
+            lambda i, p, c: es[i].ae_return_pack(_ptr(lead[i]), lead[i].numel(), p, c))
+        for a, b, c in zip(dsz, lsz, rsz):
+            self.wire.add_ae(a, b, c)
+        if self.trace_ae and any(x.numel() for x in dig):
+            self.ae_trace.append(tuple([x.cpu().numpy().tobytes() for x in inb] for inb in (dig, lead, ret)))
+        for e, x, y in zip(es, lead, ret):
+            e.ae_merge(_ptr(x), x.numel(), _ptr(y), y.numel())
+
+    def _push_pull(self):
+        """The push-pull steps of a round and its end. With every host of the cluster locked (one
+        census reduction) every pair fails: the counts only. Otherwise the chain runs once over the
+        round's matching, or in GX_PP_INITIATE once per batch of the round's exchanges, in batch
+        order (a batch sees the rows as the one before left them; every shard derives the same
+        batches, so every rank makes the same collectives)."""
+        es = self.engines
+        initiate = self.G > 1 and es[0].params.push_pull_mode == PP_INITIATE
+        nb = es[0].ae_batches() if initiate else 1  # host-only; 0: nobody's timer fires this round
+        if nb == 0:
+            pass
+        elif self.G > 1 and self.skip_locked and lock_shortcut(es[0].params) and \
                 int(self._reduce(torch.tensor([[e.lock_census()] for e in es], dtype=torch.int64), "sum")) == 0:
             for e in es:
                 e.ae_skip_locked()
             self.ae_skipped += 1
+        elif initiate:
+            for _ in range(nb):
+                self._ae_chain()
+                self.ae_batches_run += 1
         else:
-            dsz, dig = self._exchange_sized([e.ae_bytes() for e in es], lambda i, p, c: es[i].ae_pack(p, c),
-                                            after_pack=lambda e: e.ae_merge_local())
-            lsz, lead = self._exchange_sized([e.ae_delta_bytes(_ptr(x), x.numel()) for e, x in zip(es, dig)],
-                                             lambda i, p, c: es[i].ae_delta_pack(p, c))
-            rsz, ret = self._exchange_sized(
-                [e.ae_return_bytes(_ptr(x), x.numel()) for e, x in zip(es, lead)],
-                lambda i, p, c: es[i].ae_return_pack(_ptr(lead[i]), lead[i].numel(), p, c))
-            for a, b, c in zip(dsz, lsz, rsz):
-                self.wire.add_ae(a, b, c)
-            if self.trace_ae and any(x.numel() for x in dig):
-                self.ae_trace.append(tuple([x.cpu().numpy().tobytes() for x in inb] for inb in (dig, lead, ret)))
-            for e, x, y in zip(es, lead, ret):
-                e.ae_merge(_ptr(x), x.numel(), _ptr(y), y.numel())
+            self._ae_chain()
         for e in es:
             e.round_end()
 
