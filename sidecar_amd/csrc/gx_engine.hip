@@ -173,6 +173,7 @@ struct gx_engine {
   bool quiet_nowait;  // a bound took too long in this gx_run_rounds call: no more polling in it
   int64_t quiet_until, quiet_from;
   bool quiet_now;
+  bool quiet_send = true;  // quiet rounds launch k_send's lean instance (env GX_QUIET_SEND=0: the generic one, for A/B runs)
   uint32_t *in_cnt_buf;     // [2][Hl] inbox counts by round parity (Dev::in_cnt, in_cnt_nx)
   int async_phases;         // sharded phase calls return without waiting (gx_set_stream)
   int device;
@@ -568,19 +569,33 @@ static bool quiet_round(const gx_engine *e, bool storm) {
 }
 
 // k_send's variant. X: departures or the detector; SCAN: the round's expiry scans run in k_send's
-// prologue; own: own_class(S) when the owner ticks run there too, else 0; PLAN: send_planned.
+// prologue; own: own_class(S) when the owner ticks run there too, else 0; PLAN: send_planned;
+// quiet: the round is quiet (quiet_round, which implies plan, no x and no listener) and takes the
+// lean instance (QUIET) unless the engine was created with GX_QUIET_SEND=0.
 struct SendSel {
   bool x, scan, plan;
   int own;
+  bool quiet;
 };
 // The whole table of k_send variants: (X, PLAN) without both at once; with SCAN, VEC x EV x OWN; without
-// it one variant each (k_send's static_asserts state the same).
+// it one variant each; and QUIET beside every PLAN variant without EV: with SCAN, VEC x OWN, without
+// it one (k_send's static_asserts state the same). Lean and generic instance give identical results.
 // 4 lanes per host: measured best of 1/4/8/16/64 (profiles/send_team.sh);
 // teams of 2 / 8 lanes measured 25.6 / 28.7 vs 21.1 us (profiles/r02/gossip/send_team_ab.log)
 static void launch_send(gx_engine *e, SendSel sel, int do_bt) {
   const Dev &d = e->d;
   const unsigned g = nblk(d.Hl, 64);
   hipStream_t s = e->stream;
+  if (sel.quiet && sel.plan && !ev_of(e)) {
+    if (!sel.scan) {
+      k_send<4, false, false, false, false, 0, true, true><<<g, 256, 0, s>>>(d, do_bt);
+      return;
+    }
+    with_flag(vec_of(e), [&](auto V) {
+      with_own(sel.own, [&](auto O) { k_send<4, false, true, V(), false, O(), true, true><<<g, 256, 0, s>>>(d, do_bt); });
+    });
+    return;
+  }
   auto rest = [&](auto X, auto P) {
     if (!sel.scan) {
       k_send<4, X(), false, false, false, 0, P()><<<g, 256, 0, s>>>(d, do_bt);
@@ -625,8 +640,9 @@ static int round_send_impl(gx_engine *e) {
   // planned GetBroadcasts (send_planned): record budget, no detector or departures, re-armed
   // passes sleep; teams of 4 lanes per host
   const bool plan = !d.p.limit_bytes && d.p.retransmit_rounds > 0 && !d.departures && !d.p.fd_enable;
-  const SendSel sel{d.p.fd_enable || d.departures, scan_in_send, plan, fused ? own_class(d.S) : 0};
   e->quiet_now = quiet_round(e, storm);
+  const SendSel sel{d.p.fd_enable || d.departures, scan_in_send, plan, fused ? own_class(d.S) : 0,
+                    e->quiet_now && e->quiet_send};
   if (!fused) {
     LaunchTimer t(e, GX_K_OWNER);
     owner_launch(d, s);
@@ -1149,6 +1165,7 @@ static void create_dims(gx_engine *e, const gx_params *p) {
     e->scan_nch = d.R / 32768 < 16 ? d.R / 32768 : 16;  // the most chunks a row takes (scan_chunks)
   if (getenv("GX_KPROF"))  // diagnostics: phase marks of every k_send wave (gx_kprof_read)
     e->kprof_n = (size_t)nblk(d.Hl, 64) * 4 * 8 + GX_KPROF_MERGE_N + 3ull * d.H;  // + merge counts + push-pull blocks + scans
+  if (const char *qs = getenv("GX_QUIET_SEND")) e->quiet_send = strcmp(qs, "0") != 0;
   if (d.G > 1) {
     e->nblk = d.nblk_ae;
     e->nmw = (e->nblk + 31) / 32;

@@ -1509,7 +1509,14 @@ GXD grec plan_item(const Dev &d, const PlanCall &c, uint32_t i) {
 
 // Every lane of host idx's team calls it (team-uniform hs, peers, np); lead lane stores.
 // kb: algorithmic bytes (the caller flushes them to GX_K_SEND).
-template <int T>
+// QUIET (a quiet round, DESIGN.md §6: one shard, lock_model 1, every local host locked with a full
+// pipeline, so every peer): every call has lk == 3 and every packet is dropped at plan time, which
+// the host knows at launch. Only the sender's own state moves: the plan of each call with its FIFO,
+// sleep-ring and counter updates, and the ring writes of batch records left pending, exactly as in
+// the generic instance. No peer lock word is loaded (the peers themselves are not read, only their
+// count), the plan stays in registers, and the record phase, the headers and the planned send
+// buffer are compiled out.
+template <int T, bool QUIET = false>
 GXD void send_planned(const Dev &d, Acc &a, uint32_t idx, gx_host_state &hs, gx_job *pjs, PlanCall *pl,
                       const uint32_t *peers, uint32_t np, unsigned long long &kb, unsigned long long &kl,
                       uint32_t npf0 = 0) {
@@ -1531,12 +1538,12 @@ GXD void send_planned(const Dev &d, Acc &a, uint32_t idx, gx_host_state &hs, gx_
   bool stop = np == 0;
   unsigned fm = 0, fs = 0, nlines = 0;
   GX_SPLIT_DECL
-  const bool lmod = d.p.lock_model != 0;
+  const bool lmod = QUIET || d.p.lock_model != 0;
   // The planned exchange packed here (Dev::ob_buf; GossipMessages 1, so entry j = peer j): every
   // peer on another shard gets a slot of its shard's region up front (lane tl claims for peers
   // tl + T * r), written with the packet's header and records, or as an empty slot at the end.
   constexpr int NR = (16 + T - 1) / T;
-  const bool direct = d.ob_buf != nullptr;
+  const bool direct = !QUIET && d.ob_buf != nullptr;
   uint32_t osl[NR];
   uint32_t emit = 0;  // team-uniform: peers whose packet went into its slot
 #pragma unroll
@@ -1599,8 +1606,8 @@ GXD void send_planned(const Dev &d, Acc &a, uint32_t idx, gx_host_state &hs, gx_
   // A locked receiver whose pipeline was full when the round began (its count changes only in the
   // merge) drops every record of this round (memberlist's handoff queue): the call's packet is
   // counted as dropped here and neither stored nor registered (bit j of fullm).
-  uint32_t lkm = 0, fullm = 0;
-  for (uint32_t j0 = 0; j0 < np; j0 += T) {
+  uint32_t lkm = QUIET ? ~0u : 0u, fullm = lkm;  // (QUIET: known, nothing to load)
+  for (uint32_t j0 = 0; !QUIET && j0 < np; j0 += T) {
     const uint32_t jj = j0 + tl;
     const uint32_t lw = jj < np && peers[jj] - d.lo < d.Hl ? gld(&hst(d, peers[jj])->lock) : 0u;
     const bool lk = locked_in(d, lw);
@@ -1641,6 +1648,8 @@ GXD void send_planned(const Dev &d, Acc &a, uint32_t idx, gx_host_state &hs, gx_
     // ---- 1. plan up to PLAN_CH calls (control state only)
     uint32_t nc = 0, tot = 0;
     bool any_push = false;
+    PlanCall cp;  // QUIET: the chunk's call that leaves batch records pending (its last), in registers
+    cp.push = 0;
     while (nc < PLAN_CH && !stop) {
       PlanCall c;
       c.kind = 0xffu;
@@ -1650,7 +1659,7 @@ GXD void send_planned(const Dev &d, Acc &a, uint32_t idx, gx_host_state &hs, gx_
       c.m = 0;
       c.push = 0;
       c.peer = peers[j];
-      c.row = c.peer - d.lo < d.Hl ? &d.view[(size_t)(c.peer - d.lo) * d.R] : nullptr;
+      c.row = !QUIET && c.peer - d.lo < d.Hl ? &d.view[(size_t)(c.peer - d.lo) * d.R] : nullptr;
       c.lk = ((lkm >> j) & 1u) | (lmod ? ((fullm >> j) & 1u) << 1 : 0u);
       c.x = idx * d.KE + j * d.NG + n;
       c.key = u * d.KE + j * d.NG + n;
@@ -1763,7 +1772,11 @@ GXD void send_planned(const Dev &d, Acc &a, uint32_t idx, gx_host_state &hs, gx_
       c.lpre = tot;
       if (l) {  // (a dropped packet stays in the plan for its pending-ring writes; no record of it loads)
         if (c.oslot != GX_NOSLOT) emit |= 1u << j;
-        if (lead) pl[nc] = c;
+        if constexpr (QUIET) {
+          if (c.push) cp = c;
+        } else {
+          if (lead) pl[nc] = c;
+        }
         nc++;
         if (!(c.lk & 2u)) tot += l;
       }
@@ -1784,6 +1797,23 @@ GXD void send_planned(const Dev &d, Acc &a, uint32_t idx, gx_host_state &hs, gx_
       if (pushed) break;
     }
     if (nc == 0) break;
+    if constexpr (QUIET) {  // tot == 0: no record, no header; the ring writes as below, from cp
+#ifndef GX_SEND_SPLIT
+      if (j <= PLAN_CH) {
+        GX_KP(5);
+        GX_KP(6);
+      }
+#endif
+      GX_SPLIT(0);
+      // (position p is always written by lane p % T, so a later chunk's write of it follows in
+      // program order; nothing reads the ring in this launch)
+      for (uint32_t qq = (tl - cp.nh) & (T - 1); qq < cp.push; qq += T) {
+        dq[(cp.nh + qq) & mask] = plan_item(d, cp, cp.l + qq);
+        kb += 16;
+      }
+      GX_SPLIT(3);
+      continue;  // (the rest of the loop body is unreachable in this instance)
+    }
     wave_sync();  // the plan in LDS
 #ifndef GX_SEND_SPLIT
     if (j <= PLAN_CH) GX_KP(5);
@@ -1970,7 +2000,11 @@ GXD void send_planned(const Dev &d, Acc &a, uint32_t idx, gx_host_state &hs, gx_
 GXD bool filt_used(const Dev &d, uint32_t pos) { return d.sfilt && pos != 0xffffffffu; }
 // PLAN: send_planned (the engine picks it when its conditions hold: record budget, !X, retransmit
 // sleep > 0, senders' filter).
-template <int T, bool X, bool PLAN = false, bool FWD = false>
+// QUIET (with PLAN; send_planned): the message entries' length and key are not written either.
+// Their only readers are the outbox kernels of a sharded engine (ob_dest, pack_slot), and quiet
+// rounds need one shard (quiet_params), where every entry that launches them returns first.
+#define PLAN_PEERS(QUIET) ((QUIET) ? 0 : PLAN_CH)  // the team's peers slot behind its chunk plans (none kept in LDS when QUIET)
+template <int T, bool X, bool PLAN = false, bool FWD = false, bool QUIET = false>
 GXD void send_host(const Dev &d, Acc &a, uint32_t idx, gx_job *pjs, int do_bt, unsigned &lost, PlanCall *pl,
                    unsigned long long &kb, unsigned long long &kl, const TickFwd &fwd, uint32_t &quiet) {
   const uint32_t lane = threadIdx.x & (T - 1);
@@ -1982,7 +2016,7 @@ GXD void send_host(const Dev &d, Acc &a, uint32_t idx, gx_job *pjs, int do_bt, u
     gx_host_state hs = FWD ? fwd.hs : *h;
     const bool tick = do_bt && (FWD ? fwd.tick != 0 : d.tick[idx] != 0);
     bool pre = FWD;  // the FIFO head jobs the tick loaded are still at the head
-    for (uint32_t j = lane; j < d.KG; j += T) {  // (the probe entries past KG were written by k_probe)
+    for (uint32_t j = lane; !QUIET && j < d.KG; j += T) {  // (the probe entries past KG were written by k_probe)
       d.msg_len[(size_t)idx * d.KE + j] = 0;
       d.msg_key[(size_t)idx * d.KE + j] = u * d.KE + j;
     }
@@ -2007,9 +2041,9 @@ GXD void send_host(const Dev &d, Acc &a, uint32_t idx, gx_job *pjs, int do_bt, u
     if (lane == 0) kb += 128;  // the host's bookkeeping read and written
     GX_KP(4);
     if (PLAN) {
-      uint32_t *peers = reinterpret_cast<uint32_t *>(&pl[PLAN_CH]);  // the team's peers (k_send's prologue)
+      uint32_t *peers = reinterpret_cast<uint32_t *>(&pl[PLAN_PEERS(QUIET)]);  // the team's peers (k_send's prologue)
       const uint32_t np = peers[16];
-      send_planned<T>(d, a, idx, hs, pjs, pl, peers, np, kb, kl, (pre && fwd.pf0 == hs.fifo_head) ? fwd.npf : 0u);
+      send_planned<T, QUIET>(d, a, idx, hs, pjs, pl, peers, np, kb, kl, (pre && fwd.pf0 == hs.fifo_head) ? fwd.npf : 0u);
       hs.lock = lock_snap(hs.lock, hs.flags, d.round + 1, d.p.lock_readers != 0);  // the lock for the next round
       if (lane == 0) *h = hs;
       if (lane == 0 && d.p.lock_model) quiet = quiet_term(d, idx, hs);  // (planned sends only: the other paths fold 0)
@@ -2109,15 +2143,20 @@ GXD void send_host(const Dev &d, Acc &a, uint32_t idx, gx_job *pjs, int do_bt, u
 // listeners): the block's hosts tick with the same 4-lane teams, OWN services per lane, then the
 // block scans its queued views and sends. Nothing of one host's tick or send reads another host's
 // state except the receivers' inbox counts, zeroed a round ahead (Dev::in_cnt_nx).
-template <int T, bool X, bool SCAN = false, bool VEC = false, bool EV = false, int OWN = 0, bool PLAN = false>
+// QUIET: the lean planned sends of a quiet round (send_planned); the owner ticks and the scan prologue
+// are the generic ones.
+template <int T, bool X, bool SCAN = false, bool VEC = false, bool EV = false, int OWN = 0, bool PLAN = false,
+          bool QUIET = false>
 __global__ __launch_bounds__(256) void k_send(Dev d, int do_bt) {
   // the variants the host builds (launch_send): VEC, EV and OWN only shape the scans and owner ticks
-  // that SCAN brings in, and planned sends run without departures or the detector
+  // that SCAN brings in, planned sends run without departures or the detector, and quiet rounds are
+  // planned and have no listener
   static_assert(SCAN || (!VEC && !EV && OWN == 0), "k_send: VEC, EV and OWN need SCAN");
   static_assert(!(PLAN && X), "k_send: PLAN runs without departures or the detector (X)");
+  static_assert(!QUIET || (PLAN && !EV), "k_send: QUIET needs PLAN and runs without listeners (EV)");
   __shared__ gx_job s_pj[256 / T][T * GX_JPF];  // FIFO head jobs of the block's hosts, loaded ahead
   // send_planned's chunk plans, then the team's peers (16 u32 = one PlanCall's 64 B)
-  __shared__ PlanCall s_pl[PLAN ? 256 / T : 1][PLAN_CH + 1];
+  __shared__ PlanCall s_pl[PLAN ? 256 / T : 1][PLAN_PEERS(QUIET) + 1];
   __shared__ ScanLds sm;
   __shared__ uint32_t s_scan[256 / T], s_nscan;
   __shared__ gx_sleeper s_sl[OWN ? 256 * GX_JPF : 1];  // sleep-ring heads of the owner ticks
@@ -2126,7 +2165,7 @@ __global__ __launch_bounds__(256) void k_send(Dev d, int do_bt) {
   unsigned lost = 0;
   GX_KP(0);
   TickFwd fwd;
-  fwd.peers = reinterpret_cast<uint32_t *>(&s_pl[PLAN ? threadIdx.x / T : 0][PLAN_CH]);
+  fwd.peers = reinterpret_cast<uint32_t *>(&s_pl[PLAN ? threadIdx.x / T : 0][PLAN_PEERS(QUIET)]);
   if (PLAN && OWN == 0 && (threadIdx.x & (T - 1)) == 0 && idx < d.Hl) {  // the sends' peers (count in [16])
     uint32_t pr[16];
     const uint32_t np = sample_peers_h(d, peer_seed(d), d.lo + idx, pr);
@@ -2188,8 +2227,8 @@ __global__ __launch_bounds__(256) void k_send(Dev d, int do_bt) {
   uint32_t quiet = idx < d.Hl && (threadIdx.x & (T - 1)) == 0 ? 0u : 0xffffffffu;
   GX_KP(3);
   if (idx < d.Hl)  // (PLAN runs without departures: every host ticked)
-    send_host<T, X, PLAN, PLAN && (OWN > 0)>(d, a, idx, s_pj[threadIdx.x / T], do_bt, lost,
-                                            s_pl[PLAN ? threadIdx.x / T : 0], kb, kl, fwd, quiet);
+    send_host<T, X, PLAN, PLAN && (OWN > 0), QUIET>(d, a, idx, s_pj[threadIdx.x / T], do_bt, lost,
+                                                   s_pl[PLAN ? threadIdx.x / T : 0], kb, kl, fwd, quiet);
   GX_KP(7);
   acc_flush(d, a);
   if (d.p.lock_model) {  // the wave's term of the round's bound (Dev::quiet_w): a plain store per wave (2048
@@ -2205,7 +2244,7 @@ __global__ __launch_bounds__(256) void k_send(Dev d, int do_bt) {
   kb = wave_sum(kb);
   kl = wave_sum(kl);
   if ((threadIdx.x & 63) == 0) kbytes(d, GX_K_SEND, kb, kl);
-  if (PLAN && d.ob_buf) {  // the last block to finish: every region filled exactly, claims reset
+  if (PLAN && !QUIET && d.ob_buf) {  // the last block to finish: every region filled exactly, claims reset
     __shared__ uint32_t s_last;
     __syncthreads();
     if (threadIdx.x == 0) {
