@@ -316,8 +316,15 @@ typedef struct gx_params {
    *     when every slot is taken. When an exchange runs, what the unlocked side does, when the
    *     waiting merge runs and what it holds of the pipeline are as with 1; with lock_defer_slots = 1
    *     the two policies are the same, and while neither loses a merge they give the same run.
-   * 0 (default) = every exchange with a locked side fails, the round-5 model. Unsharded engines
-   * only (GX_EINVAL otherwise). lock_defer_slots: 1..4096 (0 = 64). */
+   * 0 (default) = every exchange with a locked side fails, the round-5 model.
+   * Sharded engines (the HIP engine; the oracle answers GX_EINVAL) run lock_readers = 1 without the
+   * failure detector: the pool is the cluster's, every shard holds lock_defer_slots rows and keeps
+   * the merges of its own hosts in them, and the shards arbitrate the slots in every run of the
+   * push-pull chain (the sharded rounds below: gx_ae_claim_want, gx_ae_claim_set), so slot v %
+   * lock_defer_slots is free iff no host of any shard holds it and the lowest claimant of the
+   * cluster gets it: the unsharded run, bit for bit, losses included. lock_readers = 2, and
+   * lock_readers with fd_enable, are GX_EINVAL on a sharded engine. lock_defer_slots: 1..4096
+   * (0 = 64). */
   uint32_t lock_readers;
   uint32_t lock_defer_slots;
   /* lock_model = 1 with fd_enable, unsharded engines: memberlist's own alive / suspect / dead
@@ -504,12 +511,23 @@ int gx_run_rounds(gx_engine *e, uint32_t n_rounds);
  *           host) and the pair runs (path up, partner ALIVE in the initiator's list); the other
  *           side follows it, and a pair that does not run ships no blocks. Bit 1 of `runs`: the
  *           sender's host holds the ServicesState lock this round (lock_model): the pair fails, and
- *           with lock_model = 1 the sender's digests are all zero (its row is not read).
+ *           with lock_model = 1 the sender's digests are all zero (its row is not read). Bit 2 of
+ *           `runs` (lock_readers only, else 0): the sender's host is locked, only read-locked, and
+ *           no writer waits (lock_readers above); it then sends its real digests. Both sides derive
+ *           one verdict from the two words: a locked side without bit 2 fails the pair, as above;
+ *           otherwise the pair runs, and the sides with bit 1 are its read-locked sides.
  *   lead:   u32 pair index, u32 host, u32 n_lead, u32 0, then n_lead encoded blocks (below): the
  *           row's blocks whose digests differ from the partner's and that this side leads,
  *           ascending. The side whose block has fewer literals leads it (the count rides in the
  *           digest); on a tie the pair's first host. A lead block encodes the sender's own words
- *           (own bits = the padding past the row's end). Grouped like the digests.
+ *           (own bits = the padding past the row's end). Grouped like the digests. In a pair with
+ *           a read-locked side (lock_readers) a side leads every differing block whose partner is
+ *           read-locked, and nothing else: the unlocked partner of a read-locked side leads them
+ *           all and merges the returns; the read-locked side returns its words, leads nothing,
+ *           and keeps for its waiting merge its own row with the partner's lead blocks laid over
+ *           it, every word literal (an own slot of a return is only right for a merge made at
+ *           exchange time). With both sides read-locked both lead every differing block, the return
+ *           messages carry no block, and nobody merges.
  *   return: per destination shard a table of u64 message sizes (one per pair, in message order),
  *           then the messages: u32 pair index, u32 host, u32 n_ret, u32 0, then n_ret u32 literal
  *           counts (padded with a 0 to an even number), then n_ret encoded blocks: for each block
@@ -566,6 +584,21 @@ int gx_round_merge(gx_engine *e); /* phase 4: gather-then-merge of local + recei
  * header's declarations like its diagnostics (the oracle has no such symbol): *n = 0 when the
  * round has no push-pull or nobody initiates, 1 for the matching, the batch count with
  * GX_PP_INITIATE; computed on the host from (seed, round), no device wait, equal on every shard.
+ * With lock_readers = 1 two more such symbols sit between gx_ae_delta_bytes (which tells a shard its
+ * cross pairs' verdicts) and gx_ae_merge, in every run of the chain on every shard, with or without
+ * pairs of its own: gx_ae_claim_want(e, int64_t *want) writes lock_defer_slots entries (device
+ * memory): -1 for a slot that one of this shard's hosts holds, else the lowest host id among this
+ * shard's claimants of the slot in this run (the read-locked sides of its local and cross pairs),
+ * else 2^62; the exchange layer takes the minimum over all shards; gx_ae_claim_set(e, const int64_t
+ * *won) admits the claimants that equal won[v % lock_defer_slots], counts the others in
+ * ae_defer_lost (each on its own shard) and runs the shard-local read-locked exchanges, which wait
+ * for it instead of running with the other local pairs. gx_ae_merge then builds the pool rows of the
+ * admitted sides of cross pairs. ae_exchanges of such a pair is counted by the shard of its first
+ * host, ae_deferred by the read-locked side's. gx_ae_ro_counts(e, uint64_t out[3]) reads three
+ * counters kept for the exchange layer (a synchronizing call): cross-shard exchanges that ran with
+ * a read-locked side, their sides admitted to the pool, and sides of this shard that lost their
+ * merge to a host of another shard (the slot's holder or a lower claimant). gx_ae_skip_locked does
+ * not stand for a round with lock_readers: exchanges between read-locked hosts run.
  * Digest of block b = slots [b*512, min(R, (b+1)*512)) of a row, i = slot index in the row,
  * w = slot word, sums mod 2^64, L = literal count of the block's lead encoding, u32 arithmetic
  * mod 2^32 in h: x = w ^ (i << 40) ^ i, lo/hi = its halves, a = (lo ^ rotl32(hi, 16)) * 0x85EBCA6B,

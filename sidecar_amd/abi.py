@@ -853,6 +853,26 @@ class Engine:
         check(self.lib.gx_ae_batches(self.h, C.byref(n)), "gx_ae_batches")
         return int(n.value)
 
+    def ae_claim_want(self, ptr: int):
+        """lock_readers on a sharded engine: lock_defer_slots int64 entries at ptr (device memory), per
+        pool slot -1 when a host of this shard holds it, else this shard's lowest claimant in this run
+        of the chain, else 2^62 (gx_ae_claim_want: a symbol of the HIP engine, not in gx.h's
+        declarations). The minimum over the shards goes to ae_claim_set."""
+        check(self.lib.gx_ae_claim_want(self.h, C.c_void_p(ptr)), "gx_ae_claim_want")
+
+    def ae_claim_set(self, ptr: int):
+        """Admit the claimants named in the reduced vector at ptr, count the others lost, run the local
+        read-locked exchanges (gx_ae_claim_set, between ae_delta_bytes and ae_merge)."""
+        check(self.lib.gx_ae_claim_set(self.h, C.c_void_p(ptr)), "gx_ae_claim_set")
+
+    def ae_ro_counts(self):
+        """(cross-shard read-locked exchanges that ran, counted by the shard of the pair's first host;
+        read-locked sides of cross pairs admitted to the pool; sides of this shard that lost their
+        merge to a host of another shard), since the engine was made (gx_ae_ro_counts; waits)."""
+        out = (C.c_uint64 * 3)()
+        check(self.lib.gx_ae_ro_counts(self.h, out), "gx_ae_ro_counts")
+        return int(out[0]), int(out[1]), int(out[2])
+
     def set_stream(self, stream_ptr, async_phases: bool):
         """Run this engine's device work on the caller's HIP stream (0 = the default stream; None =
         the engine's own); with async_phases the sharded phase calls return once queued (gx.h)."""

@@ -218,6 +218,11 @@ struct gx_engine {
   uint64_t *ae_off;    // [4][Hl] lead offsets, lead inbox offsets, return offsets, return table entries
   uint64_t *ae_rioff;  // [Hl] return inbox offsets
   uint32_t *ae_err;
+  // gx.h lock_readers on a sharded engine: each cross pair's read-locked verdict (k_ae_mask<true>) and
+  // the driver's counters (gx_ae_ro_counts)
+  uint8_t *ae_rov;             // [pairs] 1: this side is read-locked | 2: the partner is; 0: another verdict
+  unsigned long long *ro_xc;   // [3]
+  int64_t ae_claim_round = -1; // the step gx_ae_claim_set last ran for (ae_step)
   std::vector<uint32_t> pack_gstart;  // pack index range per destination shard
   std::vector<uint64_t> delta_off_h;
   uint64_t delta_total, lead_in_total, ret_total;
@@ -1072,9 +1077,10 @@ static int check_params(const gx_params *p) {
     return GX_EINVAL;
   if (p->push_pull_stagger > 1 || (p->push_pull_stagger && (p->push_pull_mode != GX_PP_INITIATE || !p->ae_period_rounds)))
     return GX_EINVAL;
-  if (p->lock_readers > GX_LOCK_READERS_CLAIMED || (p->lock_readers && (!p->lock_model || p->n_shards > 1)) ||
-      p->lock_defer_slots > GX_POOL_MAX)
-    return GX_EINVAL;  // gx.h lock_readers (either pool policy): unsharded engines with the lock modelled
+  if (p->lock_readers > GX_LOCK_READERS_CLAIMED || (p->lock_readers && !p->lock_model) || p->lock_defer_slots > GX_POOL_MAX)
+    return GX_EINVAL;  // gx.h lock_readers (either pool policy): with the lock modelled
+  if (p->lock_readers && p->n_shards > 1 && (p->lock_readers == GX_LOCK_READERS_CLAIMED || p->fd_enable))
+    return GX_EINVAL;  // sharded engines: the direct-mapped pool, without the failure detector
   if (p->fd_handoff_shared > 1 || (p->fd_handoff_shared && (!p->fd_enable || !p->lock_model || p->n_shards > 1)))
     return GX_EINVAL;  // gx.h fd_handoff_shared
   if (p->fd_enable) {
@@ -1291,6 +1297,10 @@ static int create_buffers(gx_engine *e) {
     TAKE(e->ae_off, sizeof(uint64_t) * 4 * H);
     TAKE(e->ae_rioff, sizeof(uint64_t) * H);
     TAKE(e->ae_err, sizeof(uint32_t));
+    if (p->lock_readers) {
+      TAKE(e->ae_rov, np, 0, s);
+      TAKE(e->ro_xc, sizeof(unsigned long long) * 3, 0, s);
+    }
   }
   return GX_OK;
 }
@@ -2388,9 +2398,10 @@ int gx_ae_pack(gx_engine *e, void *buf, uint64_t cap) {
   if (!e->n_pack) return GX_OK;
   if (e->ae_planned_round != ae_step(e) || cap < e->n_pack * dig_bytes(e)) return GX_EINVAL;
   HIPCHK(hipSetDevice(e->device));
-  with_flag(vec_of(e), [&](auto V) {
-    k_ae_digest<V()><<<e->n_pack, 256, 0, e->stream>>>(e->d, e->ae_pack_host, e->ae_pack_t, e->ae_pack_other,
-                                                        e->ae_pack_first, (uint8_t *)buf, e->ae_dig, e->nblk, e->ae_bcnt);
+  with_flags(vec_of(e), e->d.p.lock_readers != 0, [&](auto V, auto RO) {
+    k_ae_digest<V(), RO()><<<e->n_pack, 256, 0, e->stream>>>(e->d, e->ae_pack_host, e->ae_pack_t, e->ae_pack_other,
+                                                              e->ae_pack_first, (uint8_t *)buf, e->ae_dig, e->nblk,
+                                                              e->ae_bcnt);
   });
   return phase_done(e);
 }
@@ -2410,10 +2421,16 @@ int gx_ae_delta_bytes(gx_engine *e, const void *digests, uint64_t bytes, uint64_
   std::vector<uint64_t> sz(2 * (size_t)np);
   if (np) {
     HIPCHK(hipMemsetAsync(e->ae_err, 0, sizeof(uint32_t), e->stream));
-    k_ae_mask<<<np, 256, 0, e->stream>>>(d, (const uint8_t *)digests, e->ae_dig, e->ae_pack_t, e->ae_pack_host,
-                                         e->ae_pack_other, e->ae_pack_first, e->nblk, e->nmw, e->ae_mask,
-                                         e->ae_fmask, e->ae_lt, e->ae_cnt, e->ae_nfol, e->ae_sz, e->ae_sz + np,
-                                         e->ae_err, e->ae_skip);
+    if (d.p.lock_readers)  // the read-locked verdicts as well (gx.h lock_readers)
+      k_ae_mask<true><<<np, 256, 0, e->stream>>>(d, (const uint8_t *)digests, e->ae_dig, e->ae_pack_t, e->ae_pack_host,
+                                                 e->ae_pack_other, e->ae_pack_first, e->nblk, e->nmw, e->ae_mask,
+                                                 e->ae_fmask, e->ae_lt, e->ae_cnt, e->ae_nfol, e->ae_sz, e->ae_sz + np,
+                                                 e->ae_err, e->ae_skip, e->ae_rov, e->ro_xc);
+    else
+      k_ae_mask<><<<np, 256, 0, e->stream>>>(d, (const uint8_t *)digests, e->ae_dig, e->ae_pack_t, e->ae_pack_host,
+                                             e->ae_pack_other, e->ae_pack_first, e->nblk, e->nmw, e->ae_mask,
+                                             e->ae_fmask, e->ae_lt, e->ae_cnt, e->ae_nfol, e->ae_sz, e->ae_sz + np,
+                                             e->ae_err, e->ae_skip);
     if (pp_state(d))  // the partners' member lists ride with their digests
       k_fd_rsnap<<<1024, 256, 0, e->stream>>>(d, (const uint8_t *)digests, dig_bytes(e), e->nblk, np, e->fd_rsnap);
     uint32_t err = 0;
@@ -2517,18 +2534,12 @@ int gx_ae_return_pack(gx_engine *e, const void *lead, uint64_t lead_bytes, void 
   return phase_done(e);
 }
 
-// Launch the planned pairs [lo, hi) (received-row pairs first, then shard-local pairs).
-static void ae_plan_launch(gx_engine *e, uint32_t lo, uint32_t hi, const void *lead, const void *ret,
-                           hipStream_t st = nullptr) {
-  if (hi <= lo) return;
-  if (!st) st = e->stream;
-  set_round_fields(e);
-  LaunchTimer t(e, GX_K_AE, st);
-  const uint32_t np = e->n_pack;
+// The cross pairs' inboxes and per-pair tables, as the kernels that rebuild a partner's row take them.
+static AeIn ae_in(const gx_engine *e, const void *lead, const void *ret) {
   AeIn in;
   in.lead = (const uint8_t *)lead;
   in.ret = (const uint8_t *)ret;
-  in.ioff = e->ae_off + np;
+  in.ioff = e->ae_off + e->n_pack;
   in.rioff = e->ae_rioff;
   in.lmask = e->ae_mask;
   in.fmask = e->ae_fmask;
@@ -2537,10 +2548,31 @@ static void ae_plan_launch(gx_engine *e, uint32_t lo, uint32_t hi, const void *l
   in.bcnt = e->ae_bcnt;
   in.nmw = e->nmw;
   in.nblk = e->nblk;
+  return in;
+}
+// Launch the planned pairs [lo, hi) (received-row pairs first, then shard-local pairs).
+static void ae_plan_launch(gx_engine *e, uint32_t lo, uint32_t hi, const void *lead, const void *ret,
+                           hipStream_t st = nullptr) {
+  if (hi <= lo) return;
+  if (!st) st = e->stream;
+  set_round_fields(e);
+  LaunchTimer t(e, GX_K_AE, st);
+  const AeIn in = ae_in(e, lead, ret);
   // fewer than 4 pairs per CU: per-block bandwidth decides (2 tiles in flight measured slower for
   // the cross pairs of a post-heal round: 8.2 -> 9.3 ms at G = 2, H = 16384)
   const bool small = hi - lo < 1024;
   launch_ae_plan(e, small, hi - lo, st, e->ae_pa + lo, e->ae_pb + lo, e->ae_prow + lo, e->ae_pcount + lo, in, e->ae_skip);
+}
+
+// gx.h lock_readers: the pool rows of the cross pairs' admitted read-locked sides (k_ae_xdefer)
+static void ae_xdefer_launch(gx_engine *e, const void *lead) {
+  if (!e->n_pack) return;
+  set_round_fields(e);
+  LaunchTimer t(e, GX_K_AE);
+  const AeIn in = ae_in(e, lead, nullptr);
+  with_flag(vec_of(e), [&](auto V) {
+    k_ae_xdefer<V()><<<e->n_pack, 256, 0, e->stream>>>(e->d, e->ae_pack_host, e->ae_pack_first, e->ae_rov, in, e->ro_xc);
+  });
 }
 
 int gx_ae_merge_local(gx_engine *e) {
@@ -2593,6 +2625,10 @@ int gx_ae_merge(gx_engine *e, const void *lead, uint64_t lead_bytes, const void 
     if (o != ret_bytes) return GX_EINVAL;
     HIPCHK(hipMemcpy(e->ae_rioff, rio.data(), sizeof(uint64_t) * np, hipMemcpyHostToDevice));
   }
+  if (e->d.p.lock_readers) {  // the admitted read-locked sides of cross pairs keep their partners' rows
+    if (e->ae_claim_round != ae_step(e)) return GX_EINVAL;  // gx_ae_claim_want, gx_ae_claim_set come first
+    ae_xdefer_launch(e, lead);
+  }
   bool local_done = e->ae_local_round == ae_step(e);
   ae_plan_launch(e, 0, local_done ? e->n_plan_rows : e->n_plan, lead, ret);
   if (pp_state(e->d) && e->n_plan) {  // pushPull's membership half, every planned pair
@@ -2604,6 +2640,62 @@ int gx_ae_merge(gx_engine *e, const void *lead, uint64_t lead_bytes, const void 
   if (jr) return jr;
   if (e->d.p.push_pull_mode == GX_PP_INITIATE) e->pp_cursor++;  // the chain's next run takes the next batch
   return phase_done(e);
+}
+
+// gx.h lock_readers = 1 on a sharded engine (outside gx.h's declarations, described there with the
+// sharded rounds): the cluster-wide pool's arbitration, between gx_ae_delta_bytes and gx_ae_merge in
+// every run of the chain. gx_ae_claim_want writes lock_defer_slots int64 entries at `want` (device
+// memory): -1 for a slot one of this shard's hosts holds, else this shard's lowest claimant of the
+// slot in this run (the read-locked sides of its local and cross pairs), else 2^62. The caller takes
+// the minimum over all shards and hands it to gx_ae_claim_set, which admits the claimants named in
+// it, counts the others lost and runs the local read-locked exchanges (k_ae_rox). A run with nothing
+// planned on this shard still answers (held slots, no claimants) and sets nothing.
+static bool ae_claims_on(const gx_engine *e) { return e->d.G > 1 && e->d.p.lock_readers; }
+int gx_ae_claim_want(gx_engine *e, int64_t *want) {
+  if (!e || !want || !ae_claims_on(e)) return GX_EINVAL;
+  HIPCHK(hipSetDevice(e->device));
+  const bool due = ae_step_due(e);
+  if (due && (e->ae_planned_round != ae_step(e) || (e->n_pack && e->ae_delta_round != ae_step(e)))) return GX_EINVAL;
+  if (due && e->ae_local_round != ae_step(e)) {  // the local pairs' launch flags their read-locked exchanges
+    int rc = gx_ae_merge_local(e);
+    if (rc) return rc;
+  }
+  int jr = join_side(e);  // ro_flag is written
+  if (jr) return jr;
+  set_round_fields(e);
+  const uint32_t lo = due ? e->n_plan_rows : 0, nl = due ? e->n_plan - lo : 0, np = due ? e->n_pack : 0;
+  k_ae_want<<<1, 256, 0, e->stream>>>(e->d, e->ae_pa + lo, e->ae_pb + lo, nl, e->ae_pack_host, e->ae_rov, np,
+                                      (long long *)want);
+  return phase_done(e);
+}
+int gx_ae_claim_set(gx_engine *e, const int64_t *won) {
+  if (!e || !won || !ae_claims_on(e)) return GX_EINVAL;
+  HIPCHK(hipSetDevice(e->device));
+  if (!ae_step_due(e)) return GX_OK;
+  if (e->ae_planned_round != ae_step(e) || e->ae_local_round != ae_step(e) || e->side_pending) return GX_EINVAL;
+  set_round_fields(e);
+  const uint32_t lo = e->n_plan_rows, nl = e->n_plan - lo;
+  {
+    LaunchTimer t(e, GX_K_AE);
+    k_ae_claim_set<<<1, 256, 0, e->stream>>>(e->d, e->ae_pa + lo, e->ae_pb + lo, nl, e->ae_pack_host, e->ae_rov,
+                                             e->n_pack, (const long long *)won, e->ro_xc);
+    if (nl)  // the local read-locked exchanges, slots decided
+      with_flags(vec_of(e), ev_of(e), [&](auto V, auto E) {
+        k_ae_rox<V(), E()><<<ae_grid(nl, 1), 256, 0, e->stream>>>(e->d, e->ae_pa + lo, e->ae_pb + lo, 0, 0);
+      });
+  }
+  e->ae_claim_round = ae_step(e);
+  return phase_done(e);
+}
+// The driver's counters of the sharded read-locked exchanges, summed since gx_create: out[0] cross-
+// shard exchanges that ran with a read-locked side (counted by the shard of the pair's first host),
+// out[1] read-locked sides of cross pairs admitted to the pool, out[2] sides of this shard that lost
+// their merge to a host of another shard (the slot's holder, or a lower claimant). Waits for the device.
+int gx_ae_ro_counts(gx_engine *e, uint64_t *out) {
+  if (!e || !out || !ae_claims_on(e)) return GX_EINVAL;
+  HIPCHK(hipSetDevice(e->device));
+  HIPCHK(hipMemcpyAsync(out, e->ro_xc, sizeof(uint64_t) * 3, hipMemcpyDeviceToHost, e->stream));
+  return sync_check(e);
 }
 
 int gx_lock_census(gx_engine *e, uint32_t *unlocked) {
@@ -2626,7 +2718,8 @@ int gx_ae_skip_locked(gx_engine *e) {
   Dev &d = e->d;
   if (!ae_round(e)) return GX_OK;
   // sharded engines only (one engine runs its push-pull itself; the pair buffers exist when G > 1)
-  if (d.G < 2 || !e->ae_pa || !d.p.lock_model || d.departures || d.p.fd_enable) return GX_EINVAL;
+  // (nor with lock_readers: an exchange between read-locked hosts runs)
+  if (d.G < 2 || !e->ae_pa || !d.p.lock_model || d.departures || d.p.fd_enable || d.p.lock_readers) return GX_EINVAL;
   uint32_t unlocked = 0;
   int rc = gx_lock_census(e, &unlocked);
   if (rc) return rc;

@@ -4166,7 +4166,9 @@ GXD bool ae_initiator_runs(const Dev &d, uint32_t mine, uint32_t other) {
 GXHD size_t dig_stride(const Dev &d, uint32_t nblk) {
   return 16 + 16ull * nblk + (d.p.fd_enable && d.p.fd_push_pull_state ? 8ull * d.H : 0);
 }
-template <bool VEC>
+// RO (gx.h lock_readers on a sharded engine): a locked host for which ro_side holds says so in bit 2
+// of header word 3 and sends its real digests, so the exchange can run with its side read-locked.
+template <bool VEC, bool RO = false>
 __global__ __launch_bounds__(256) void k_ae_digest(Dev d, const uint32_t *host, const uint32_t *pair_t,
                                                     const uint32_t *other, const uint8_t *first, uint8_t *out,
                                                     ulonglong2 *own, uint32_t nblk, uint32_t *bcnt) {
@@ -4185,9 +4187,9 @@ __global__ __launch_bounds__(256) void k_ae_digest(Dev d, const uint32_t *host, 
     // bit 0: with the failure detector, the initiator's decision that the pair runs; bit 1: this
     // side's host holds the ServicesState lock this round (gx.h lock_model)
     hdr[3] = (d.p.fd_enable && first[k] && ae_initiator_runs(d, host[k], other[k]) ? 1u : 0u) |
-             (host_locked(d, host[k]) ? 2u : 0u);
+             (host_locked(d, host[k]) ? 2u : 0u) | (RO && ro_side(d, host[k]) ? 4u : 0u);
   }
-  if (d.p.lock_model && host_locked(d, host[k])) {  // the pair fails (gx.h digest): zero digests, no row read
+  if (d.p.lock_model && host_locked(d, host[k]) && !(RO && ro_side(d, host[k]))) {  // the pair fails (gx.h digest): zero digests, no row read
     for (uint32_t b = threadIdx.x; b < nblk; b += blockDim.x)
       *reinterpret_cast<ulonglong2 *>(msg + 16 + 16ull * b) = make_ulonglong2(0ull, 0ull);
     return;
@@ -4269,11 +4271,19 @@ __global__ void k_ae_locked_note(Dev d, uint32_t n_first, uint32_t any) {
 // leads each (fewer literals; ties: the pair's first host). Per pair: lead and follow counts, the
 // size of this side's lead message and of the partner's. A pair that does not run (failure
 // detector: the initiator's decision) ships no blocks.
+// RO (gx.h lock_readers on a sharded engine): both shards of a pair derive one verdict from the two
+// header words. A pair whose locked sides are all read-locked (bit 2) runs: rov[k] = 1 (this side is
+// read-locked) | 2 (the partner is), 0 for every other pair. A side leads every differing block whose
+// partner is read-locked and nothing else; with both sides read-locked both lead them all, nobody
+// returns anything (fmask empty: the partner's lead blocks are the blocks of lmask), and a
+// read-locked side never merges in this pass (skip bit 0). xc[0] counts these exchanges once.
+template <bool RO = false>
 __global__ __launch_bounds__(256) void k_ae_mask(Dev d, const uint8_t *in, const ulonglong2 *own,
                                                   const uint32_t *pair_t, const uint32_t *host, const uint32_t *other,
                                                   const uint8_t *first, uint32_t nblk, uint32_t nmw, uint32_t *lmask,
                                                   uint32_t *fmask, uint16_t *lt, uint32_t *nlead, uint32_t *nfol,
-                                                  uint64_t *lsz, uint64_t *isz, uint32_t *err, uint8_t *skip) {
+                                                  uint64_t *lsz, uint64_t *isz, uint32_t *err, uint8_t *skip,
+                                                  uint8_t *rov = nullptr, unsigned long long *xc = nullptr) {
   __shared__ unsigned long long s_n[4][3];
   const uint32_t k = blockIdx.x;
   const uint8_t *msg = in + (size_t)k * dig_stride(d, nblk);
@@ -4283,12 +4293,22 @@ __global__ __launch_bounds__(256) void k_ae_mask(Dev d, const uint8_t *in, const
   // the ServicesState lock (gx.h lock_model): a side that holds it fails the exchange; with
   // lock_model = 0 the pair runs and its merges count as locked (skip bit 1)
   const bool lk = runs && (host_locked(d, host[k]) || (hdr[3] & 2u) != 0);
+  bool ro = false, ro_me = false, ro_it = false;  // block-uniform
+  if (RO && lk && d.p.lock_model) {
+    ro_me = host_locked(d, host[k]);
+    ro_it = (hdr[3] & 2u) != 0;
+    ro = (!ro_me || ro_side(d, host[k])) && (!ro_it || (hdr[3] & 4u) != 0);
+  }
   if (lk && threadIdx.x == 0) {
     atomicMin(&d.ctr->first_drop[shard_id()][1], (unsigned long long)d.round);
-    if (d.p.lock_model && first[k]) ctr_atomic(d, C_AE_LOCKED, 1);
+    if (d.p.lock_model && first[k] && !ro) ctr_atomic(d, C_AE_LOCKED, 1);
+    if (RO && ro && first[k]) atomicAdd(&xc[0], 1ull);
   }
-  if (lk && d.p.lock_model) runs = false;
-  if (threadIdx.x == 0) skip[k] = (runs ? 0 : 1) | (lk && runs ? 2 : 0);
+  if (lk && d.p.lock_model && !ro) runs = false;
+  if (threadIdx.x == 0) {
+    skip[k] = RO && ro ? (ro_me ? 1 : 0) : (runs ? 0 : 1) | (lk && runs ? 2 : 0);
+    if (RO) rov[k] = ro ? (ro_me ? 1 : 0) | (ro_it ? 2 : 0) : 0;
+  }
   unsigned long long n = 0, bl = 0, bi = 0;  // n: lead count | follow count << 32
   if (!runs) {  // block-uniform: a pair that does not run leads and follows nothing (its digests unread)
     for (uint32_t w = threadIdx.x; w < nmw; w += blockDim.x) {
@@ -4306,7 +4326,14 @@ __global__ __launch_bounds__(256) void k_ae_mask(Dev d, const uint8_t *in, const
         const ulonglong2 y = *reinterpret_cast<const ulonglong2 *>(msg + 16 + 16ull * b);
         const uint32_t lm = (uint32_t)(x.y >> 54), ly = (uint32_t)(y.y >> 54);
         lt[(size_t)k * nblk + b] = (uint16_t)ly;
-        if (x.x != y.x || x.y != y.y) {
+        if (RO && ro) {
+          if (x.x != y.x || x.y != y.y) {
+            lead = ro_it;
+            fol = !ro_it;
+            if (ro_it) bl += 128 + 8ull * lm;
+            if (ro_me) bi += 128 + 8ull * ly;  // both read-locked: the partner leads the same blocks
+          }
+        } else if (x.x != y.x || x.y != y.y) {
           lead = lm < ly || (lm == ly && first[k]);
           fol = !lead;
           if (lead) bl += 128 + 8ull * lm;
@@ -4343,6 +4370,136 @@ __global__ __launch_bounds__(256) void k_ae_mask(Dev d, const uint8_t *in, const
     nfol[k] = (uint32_t)(tn >> 32);
     lsz[k] = 16 + tl;
     isz[k] = 16 + ti;
+  }
+}
+
+// gx.h lock_readers = 1 on a sharded engine: the pool is cluster-wide, so the shards arbitrate its
+// slots between gx_ae_delta_bytes (the cross pairs' verdicts, rov) and gx_ae_merge. This shard's
+// claimants of a chain pass are the read-locked sides of its local pairs flagged by the pass's launch
+// (ro_flag[j], pair j of pa/pb) and of its cross pairs (rov[k] & 1, host[k]); x wants slot x % P.
+// k_ae_want (one block) writes want[s]: GX_CLAIM_HELD (below every host id) when a host of this shard
+// holds s, else this shard's lowest claimant of s, else GX_CLAIM_NONE (above every host id). The
+// minimum over the shards is the oracle's ae_claims: a held slot stays held, a free one goes to the
+// lowest claimant of the cluster.
+#define GX_CLAIM_HELD (-1ll)
+#define GX_CLAIM_NONE (1ll << 62)
+template <class F>
+GXD void ae_claimants(const Dev &d, const uint32_t *pa, const uint32_t *pb, uint32_t n_local, const uint32_t *host,
+                      const uint8_t *rov, uint32_t n_pack, F &&f) {
+  for (uint32_t j = threadIdx.x; j < n_local; j += blockDim.x) {
+    if (!d.ro_flag[j]) continue;
+    if (host_locked(d, pa[j])) f(pa[j]);
+    if (host_locked(d, pb[j])) f(pb[j]);
+  }
+  for (uint32_t k = threadIdx.x; k < n_pack; k += blockDim.x)
+    if (rov[k] & 1u) f(host[k]);
+}
+__global__ __launch_bounds__(256) void k_ae_want(Dev d, const uint32_t *pa, const uint32_t *pb, uint32_t n_local,
+                                                  const uint32_t *host, const uint8_t *rov, uint32_t n_pack,
+                                                  long long *want) {
+  __shared__ uint32_t s_slot[GX_POOL_MAX];  // each slot's lowest claimant here
+  for (uint32_t s = threadIdx.x; s < d.P; s += blockDim.x) s_slot[s] = GX_NOHOST;
+  __syncthreads();
+  ae_claimants(d, pa, pb, n_local, host, rov, n_pack, [&](uint32_t x) { atomicMin(&s_slot[x % d.P], x); });
+  __syncthreads();
+  for (uint32_t s = threadIdx.x; s < d.P; s += blockDim.x)
+    want[s] = d.dpool_host[s] != GX_NOHOST ? GX_CLAIM_HELD : s_slot[s] == GX_NOHOST ? GX_CLAIM_NONE : (long long)s_slot[s];
+}
+// ... and k_ae_claim_set (one block) admits the claimants that equal won[x % P], the reduced vector:
+// dslot and dpool_host as k_ae_claim leaves them. Every other claimant is lost and counted here;
+// xc[2] counts those whose rival, the slot's holder or the lower claimant, lives on another shard.
+// It also lists the flagged local pairs for k_ae_rox (ro_list, *ro_n) and clears ro_flag.
+__global__ __launch_bounds__(256) void k_ae_claim_set(Dev d, const uint32_t *pa, const uint32_t *pb, uint32_t n_local,
+                                                       const uint32_t *host, const uint8_t *rov, uint32_t n_pack,
+                                                       const long long *won, unsigned long long *xc) {
+  __shared__ unsigned long long s_red[4];
+  __shared__ uint32_t s_n;
+  if (threadIdx.x == 0) s_n = 0;
+  __syncthreads();
+  uint32_t lost = 0, lost_x = 0;
+  ae_claimants(d, pa, pb, n_local, host, rov, n_pack, [&](uint32_t x) {
+    const uint32_t slot = x % d.P;
+    const long long w = won[slot];
+    if (w == (long long)x) {  // one claimant per slot at most: no other thread reads or writes these
+      d.dslot[x] = slot;
+      d.dpool_host[slot] = x;
+    } else {
+      lost++;
+      // a held slot has no winner, so nobody writes its host in this launch
+      lost_x += w == GX_CLAIM_HELD ? d.dpool_host[slot] == GX_NOHOST : (uint32_t)w - d.lo >= d.Hl;
+    }
+  });
+  for (uint32_t j = threadIdx.x; j < n_local; j += blockDim.x)
+    if (d.ro_flag[j]) {
+      d.ro_list[atomicAdd(&s_n, 1u)] = j;  // any order: the pairs are disjoint
+      d.ro_flag[j] = 0;
+    }
+  block_ctr(d, C_AE_DEFER_LOST, lost, s_red);
+  const unsigned long long lx = block_sum(lost_x, s_red);
+  if (threadIdx.x == 0) {
+    *d.ro_n = s_n;
+    if (lx) atomicAdd(&xc[2], lx);
+  }
+}
+// The read-locked side x of cross pair k (rov[k] & 1) after the arbitration: with a slot it keeps the
+// partner's pre-exchange row there, rebuilt block by block: a differing block is the partner's lead
+// block, every word a literal (the partner leads every differing block of a read-locked side, and
+// only padding past the row's end is an own slot there); every other block is x's own (the digests
+// matched). 16-B loads and nontemporal 16-B stores on even rows. x is locked and only this pair
+// could merge into its row, so the row is the pre-exchange one whenever this runs in the pass.
+// Then as k_ae_rox: min(n, 26) pipeline places, the DEFER bit, ae_deferred. Without a slot the merge
+// is lost (k_ae_claim_set counted it) and what x received is dropped. The exchange is counted by
+// the shard of the pair's first host: here when that is x. xc[1] counts the admitted sides.
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_ae_xdefer(Dev d, const uint32_t *host, const uint8_t *first,
+                                                    const uint8_t *rov, AeIn in, unsigned long long *xc) {
+  __shared__ unsigned long long s_red[4];
+  const uint32_t k = blockIdx.x, t = threadIdx.x, v = rov[k];
+  if (!(v & 1u)) return;  // block-uniform
+  const uint32_t x = host[k], slot = d.dslot[x];
+  if (t == 0 && first[k]) ctr_atomic(d, C_AEX, 1);
+  if (slot >= d.P) return;
+  const uint64_t *row = vrow(d, x);
+  uint64_t *dst = &d.dpool[(size_t)slot * d.R];
+  const uint32_t *mask = ((v & 2u) ? in.lmask : in.fmask) + (size_t)k * in.nmw;
+  const uint16_t *lt = in.lt + (size_t)k * in.nblk;
+  const uint8_t *lead = in.lead + in.ioff[k] + 16;
+  uint64_t off = 0;  // of the next lead block (block-uniform)
+  unsigned long long np = 0;
+  for (uint32_t b = 0; b < in.nblk; b++) {  // a 512-slot digest block at a time, two slots per thread
+    const uint32_t r0 = b * GX_DIGEST_SLOTS + 2 * t;
+    const bool v0 = r0 < d.R, v1 = r0 + 1 < d.R;  // (a ragged last block)
+    uint64_t w[2] = {GX_SLOT_ABSENT, GX_SLOT_ABSENT};
+    if (VEC) {
+      if (v0) {
+        const ulonglong2 p = ld16<false>(&row[r0]);
+        w[0] = p.x;
+        w[1] = p.y;
+      }
+    } else {
+      if (v0) w[0] = row[r0];
+      if (v1) w[1] = row[r0 + 1];
+    }
+    if ((mask[b >> 5] >> (b & 31)) & 1u) {
+      dec_pair_u(reinterpret_cast<const uint64_t *>(lead + off), 2 * t, v0, v1, w);
+      off += 128 + 8ull * lt[b];
+    }
+    if (VEC) {
+      typedef unsigned long long v2u64s __attribute__((ext_vector_type(2)));
+      if (v0) __builtin_nontemporal_store((v2u64s){w[0], w[1]}, reinterpret_cast<v2u64s *>(&dst[r0]));
+    } else {
+      if (v0) dst[r0] = w[0];
+      if (v1) dst[r0 + 1] = w[1];
+    }
+    np += (v0 && st_of(w[0]) != GX_ABSENT) + (v1 && st_of(w[1]) != GX_ABSENT);
+  }
+  np = block_sum(np, s_red);
+  if (t == 0) {
+    d.dpool_res[slot] = np < GX_LOCK_DEFER_RES ? (uint32_t)np : GX_LOCK_DEFER_RES;
+    hst(d, x)->lock |= GX_LOCK_DEFER_MERGE;
+    ctr_atomic(d, C_AE_DEFER, 1);
+    kbytes(d, GX_K_AE, 16ull * d.R, 0);
+    atomicAdd(&xc[1], 1ull);
   }
 }
 

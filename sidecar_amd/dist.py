@@ -39,8 +39,10 @@ def planned_exchange(p: GxParams) -> bool:
 
 def lock_shortcut(p: GxParams) -> bool:
     """A push-pull round may be replaced by gx_ae_skip_locked when every host holds the lock: the
-    lock model on, no failure detector (its membership half runs regardless), no departures."""
-    return bool(p.lock_model) and not p.fd_enable and not (p.depart_round >= 0 and p.depart_ppm)
+    lock model on, no failure detector (its membership half runs regardless), no departures, no
+    lock_readers (an exchange between read-locked hosts runs, gx.h)."""
+    return bool(p.lock_model) and not p.fd_enable and not (p.depart_round >= 0 and p.depart_ppm) and \
+        not p.lock_readers
 
 
 def _ptr(t: torch.Tensor) -> int:
@@ -122,6 +124,9 @@ class ShardRounds:
         self.ae_skipped = 0  # push-pull rounds with every host locked (gx_ae_skip_locked)
         self.skip_locked = True  # False: run the whole exchange even then (wire tests)
         self.ae_batches_run = 0  # GX_PP_INITIATE: runs of the push-pull chain, one per batch
+        # lock_readers: the pool of waiting merges is cluster-wide, so every run of the chain
+        # arbitrates its slots over all shards (_claim_slots)
+        self._arbitrate = G > 1 and bool(self.shards[0].e.params.lock_readers)
         self._pb = None
 
     @property
@@ -179,15 +184,42 @@ class ShardRounds:
             s.e.round_merge()
         return self.shards[0].e.is_ae_round()  # every shard agrees: the schedule is global
 
+    def _claim_slots(self):
+        """lock_readers: each held shard's holders and lowest claimants per pool slot, their minimum
+        over all shards, and each shard admits its claimants named in it (gx.h lock_readers). One
+        reduction in every run of the chain, whatever the device data say."""
+        es = self.engines
+        want = torch.empty((len(es), self.shards[0].e.params.lock_defer_slots or 64), dtype=torch.int64,
+                           device=self.device)
+        for e, w in zip(es, want):
+            e.ae_claim_want(_ptr(w))
+        won = self._reduce(want, "min").contiguous()
+        for e in es:
+            e.ae_claim_set(_ptr(won))  # (queued on the stream that frees `won`)
+
+    def ro_counts(self) -> dict:
+        """lock_readers: the read-locked exchanges between shards, over this process's shards since
+        they were made: those that ran (counted by the shard of the pair's first host), their sides
+        admitted to the pool, and the sides (of any pair) that lost their merge to a host of another
+        shard, the slot's holder or a lower claimant. Kept on the device by the kernels that decide
+        them; reading them waits for the device, the chain never does."""
+        keys = ("cross_exchanges", "cross_admitted", "lost_to_other_shard")
+        if not self._arbitrate:
+            return dict.fromkeys(keys, 0)
+        return dict(zip(keys, map(sum, zip(*(e.ae_ro_counts() for e in self.engines)))))
+
     def _ae_chain(self):
         """One run of the push-pull chain over the pairs the engines plan (the round's matching, or
         one batch of GX_PP_INITIATE): digests, the blocks each side leads, the partners' return
-        blocks (gx.h); shard-local pairs overlap the exchanges."""
+        blocks (gx.h); shard-local pairs overlap the exchanges. With lock_readers the pool's slots are
+        arbitrated once the digests have told each shard its cross pairs' verdicts."""
         es = self.engines
         dsz, dig = self._exchange_sized([e.ae_bytes() for e in es], lambda i, p, c: es[i].ae_pack(p, c),
                                         after_pack=lambda e: e.ae_merge_local())
-        lsz, lead = self._exchange_sized([e.ae_delta_bytes(_ptr(x), x.numel()) for e, x in zip(es, dig)],
-                                         lambda i, p, c: es[i].ae_delta_pack(p, c))
+        delta = [e.ae_delta_bytes(_ptr(x), x.numel()) for e, x in zip(es, dig)]
+        if self._arbitrate:
+            self._claim_slots()
+        lsz, lead = self._exchange_sized(delta, lambda i, p, c: es[i].ae_delta_pack(p, c))
         rsz, ret = self._exchange_sized(
             [e.ae_return_bytes(_ptr(x), x.numel()) for e, x in zip(es, lead)],
             lambda i, p, c: es[i].ae_return_pack(_ptr(lead[i]), lead[i].numel(), p, c))
