@@ -281,7 +281,13 @@ typedef struct gx_params {
    * result; a ping across the partition or to a departed host is lost after GetBroadcasts took
    * its records, and gets no ack. In byte mode the ping or ack message takes fd_msg_bytes + 2 of
    * limit_bytes. Parity unpinned (the fork is absent); 0 (default) = gossip() only, the rounds 1-5
-   * model. Unsharded engines without the failure detector only (GX_EINVAL otherwise). */
+   * model. Without the failure detector only (GX_EINVAL with fd_enable). On a sharded engine a
+   * ping or ack to a host of another shard is one more packet slot of the gossip exchange (key
+   * sender * KE + K * NG + 0 or 1, below): the receiver's shard filters it on arrival, queues it
+   * unfiltered at a locked receiver and drops and counts it at a full pipeline, like a gossip
+   * packet; a lost ping is counted by the sender's shard. gx_exchange_plan counts these slots, and
+   * the HIP engine writes them into the send buffer where it writes the gossip packets. The CPU
+   * oracle runs probe_piggyback unsharded only. */
   uint32_t probe_piggyback;
   /* GX_PP_INITIATE only: 1 = memberlist's staggered push-pull timers (pushPullTrigger waits a random
    * stagger in [0, PushPullInterval) before its first tick, so the nodes' exchanges spread over the
@@ -497,7 +503,9 @@ int gx_run_rounds(gx_engine *e, uint32_t n_rounds);
  * torch.distributed: RCCL between GPUs, gloo for the CPU oracle). Exchange buffers are device
  * memory for the HIP engine and host memory for the oracle; `bytes_per_shard` has n_shards
  * entries. Wire formats (both little-endian):
- *   packet: u32 key (= sender * fanout + j), u32 receiver, u32 len, u32 n_fd, then packet_cap x
+ *   packet: u32 key (= sender * KE + j: KE = fanout * max(1, gossip_messages) packet entries per
+ *           host, + 2 with probe_piggyback, the ping and the ack, which come last; entry j =
+ *           target * max(1, gossip_messages) + message), u32 receiver, u32 len, u32 n_fd, then packet_cap x
  *           {u64 word, u32 record key, u32 0} (the first len used); with fd_enable then fd_msg_cap x
  *           {u32 incarnation, u32 node | from << 16, u32 kind, u32 0} (the first n_fd used, the
  *           packet's memberlist messages); fixed-size slots grouped by destination shard, ascending
@@ -555,7 +563,11 @@ int gx_outbox_sizes_async(gx_engine *e, uint64_t *bytes_per_shard);
 int gx_inbox_unpack(gx_engine *e, const void *buf, uint64_t bytes);
 /* The gossip exchange with sizes every shard knows ahead, so no exchange layer waits on the device
  * for them: the packets shard s sends shard g in round n are bounded by the seeded peer sample
- * (GossipMessages slots per sampled peer of a host of s on g), which every shard can compute.
+ * (GossipMessages slots per sampled peer of a host of s on g) and, with probe_piggyback, by the
+ * seeded probe schedule (one slot for the ping of a host of s that ticks in round n and whose
+ * target is on g and on its side of the partition, one for the ack of a host of s that such a
+ * ping from g reaches; departures are not known to the plan, their slots stay empty), which every
+ * shard can compute. A shard sends at most fanout * max(1, gossip_messages) (+ 2) slots per host.
  * gx_exchange_plan fills sizes[s * G + g] = that bound in packet-slot bytes for the engine's current
  * round (from a batch of rounds computed ahead on the device); gx_outbox_pack_planned packs this
  * shard's packets for shard g into its sizes[me * G + g] bytes: the packets first (as

@@ -776,6 +776,13 @@ class Engine:
         check(self.lib.gx_xplan_waits(self.h, out), "gx_xplan_waits")
         return int(out[0]), int(out[1])
 
+    def probe_cross(self):
+        """(non-empty probe ping packets, ack packets) this engine has sent to hosts of other shards
+        since create (gx.h probe_piggyback): a diagnostics symbol of the HIP engine, not in gx.h."""
+        out = (C.c_uint64 * 2)()
+        check(self.lib.gx_probe_cross(self.h, out), "gx_probe_cross")
+        return int(out[0]), int(out[1])
+
     def outbox_pack_planned(self, ptr: int, cap: int):
         check(self.lib.gx_outbox_pack_planned(self.h, C.c_void_p(ptr), C.c_uint64(cap)), "gx_outbox_pack_planned")
 

@@ -215,6 +215,9 @@ struct Dev {
   uint8_t *ob_buf;           // the send buffer (slots of 16 + 16 * packet_cap bytes), or null
   const uint32_t *ob_cnt;    // [G] slots this shard sends each shard this round (k_xplan's row, on the device)
   uint32_t *ob_claim;        // [XPLAN_GMAX] slots claimed per destination, [XPLAN_GMAX] blocks done; reset by the last block
+  // sharded probe_piggyback: non-empty pings [0] and acks [1] sent to hosts of other shards since
+  // create (gx_probe_cross), else null
+  unsigned long long *probe_x;
   unsigned long long *kprof;  // diagnostics (env GX_KPROF): wall-clock phase marks of k_send per wave, or null
 };
 

@@ -723,7 +723,7 @@ static int round_merge_impl(gx_engine *e) {
     LaunchTimer t(e, GX_K_AE);
     with_flags(vec_of(e), ev_of(e), [&](auto V, auto E) { k_defer_drain<V(), E()><<<d.P, 256, 0, s>>>(d); });
   }
-  if (d.K) {
+  if (d.KE) {  // (fanout 0 with probe_piggyback: the pings and acks are the only packets)
     LaunchTimer t(e, GX_K_MERGE);
     // receivers routed by their live records. GossipMessages > 1: inboxes of hundreds of live
     // records, each folded by a whole wave tile by tile, so more waves in flight (16 receivers per
@@ -1073,8 +1073,8 @@ static int check_params(const gx_params *p) {
   if (p->lock_model && (((uint64_t)p->n_hosts + (p->n_shards > 1 ? p->n_shards : 1) - 1) / (p->n_shards > 1 ? p->n_shards : 1)) *
                                p->lock_buffer * 16ull > GX_LOCK_BUF_MAX_BYTES)
     return GX_EINVAL; // the pipelines' records (gx.h lock_buffer)
-  if (p->probe_piggyback > 1 || (p->probe_piggyback && (p->fd_enable || p->n_shards > 1 || p->fd_probe_rounds < 1)))
-    return GX_EINVAL;
+  if (p->probe_piggyback > 1 || (p->probe_piggyback && (p->fd_enable || p->fd_probe_rounds < 1)))
+    return GX_EINVAL;  // gx.h probe_piggyback: without the failure detector (sharded engines too)
   if (p->push_pull_stagger > 1 || (p->push_pull_stagger && (p->push_pull_mode != GX_PP_INITIATE || !p->ae_period_rounds)))
     return GX_EINVAL;
   if (p->lock_readers > GX_LOCK_READERS_CLAIMED || (p->lock_readers && !p->lock_model) || p->lock_defer_slots > GX_POOL_MAX)
@@ -1273,6 +1273,7 @@ static int create_buffers(gx_engine *e) {
     TAKE(d.in_stamp, sizeof(uint32_t) * Hg * K, 0, s);
     TAKE(e->ob_total, sizeof(uint32_t));
     TAKE(e->ob_claim, sizeof(uint32_t) * (XPLAN_GMAX + 1), 0, s);
+    if (p->probe_piggyback) TAKE(d.probe_x, sizeof(unsigned long long) * 2, 0, s);
     TAKE(e->ob_counts, sizeof(uint32_t) * d.G * (1 + 2 * ((H * K + 255) / 256)));
     const size_t np = Hg / 2 + 1;
     TAKE(e->ae_pa, sizeof(uint32_t) * np);
@@ -2111,7 +2112,7 @@ int gx_outbox_bytes(gx_engine *e, uint64_t *bytes) {
   for (uint32_t g = 0; g < d.G; g++) bytes[g] = 0;
   e->n_ob = 0;
   e->ob_async = false;
-  if (d.G < 2 || !d.K) return GX_OK;
+  if (d.G < 2 || !d.KE) return GX_OK;
   outbox_plan(e);
   std::vector<uint32_t> cnt(d.G);
   HIPCHK(hipMemcpyAsync(cnt.data(), e->ob_counts, sizeof(uint32_t) * d.G, hipMemcpyDeviceToHost, e->stream));
@@ -2132,7 +2133,7 @@ int gx_outbox_sizes_async(gx_engine *e, uint64_t *bytes) {
   Dev &d = e->d;
   e->n_ob = 0;
   e->ob_async = false;
-  if (d.G < 2 || !d.K) {
+  if (d.G < 2 || !d.KE) {
     HIPCHK(hipMemsetAsync(bytes, 0, sizeof(uint64_t) * d.G, e->stream));
     return phase_done(e);
   }
@@ -2221,7 +2222,7 @@ int gx_exchange_plan(gx_engine *e, uint64_t *sizes) {
   if (d.p.fd_enable) return GX_ENOSYS;
   if (d.G > XPLAN_GMAX) return GX_EINVAL;
   for (uint32_t i = 0; i < d.G * d.G; i++) sizes[i] = 0;
-  if (d.G < 2 || !d.K) return GX_OK;
+  if (d.G < 2 || !d.KE) return GX_OK;
   HIPCHK(hipSetDevice(e->device));
   const uint32_t *c = nullptr;
   int rc = xplan_counts(e, &c);
@@ -2236,7 +2237,7 @@ int gx_outbox_pack_planned(gx_engine *e, void *buf, uint64_t cap) {
   if (!e || (cap && !buf)) return GX_EINVAL;
   Dev &d = e->d;
   if (d.p.fd_enable) return GX_ENOSYS;
-  if (d.G < 2 || !d.K) return GX_OK;
+  if (d.G < 2 || !d.KE) return GX_OK;
   if (e->xbound_round != d.round) {  // the plan of this round, if the caller did not ask for it
     std::vector<uint64_t> tmp((size_t)d.G * d.G);
     int rc = gx_exchange_plan(e, tmp.data());
@@ -3104,6 +3105,23 @@ int gx_xplan_waits(gx_engine *e, uint64_t *out) {
   if (!e || !out) return GX_EINVAL;
   out[0] = e->xplan_waits[0];
   out[1] = e->xplan_waits[1];
+  return GX_OK;
+}
+
+// Diagnostics outside gx.h: the non-empty probe ping packets (out[0]) and ack packets (out[1]) this
+// engine has sent to hosts of other shards since create (gx.h probe_piggyback; k_probe counts them).
+// Zeros on an unsharded engine and with probe_piggyback = 0. Waits for the device.
+int gx_probe_cross(gx_engine *e, uint64_t *out) {
+  if (!e || !out) return GX_EINVAL;
+  out[0] = out[1] = 0;
+  if (!e->d.probe_x) return GX_OK;
+  HIPCHK(hipSetDevice(e->device));
+  unsigned long long c[2] = {0, 0};
+  HIPCHK(hipMemcpyAsync(c, e->d.probe_x, sizeof(c), hipMemcpyDeviceToHost, e->stream));
+  int rc = sync_check(e);
+  if (rc) return rc;
+  out[0] = c[0];
+  out[1] = c[1];
   return GX_OK;
 }
 

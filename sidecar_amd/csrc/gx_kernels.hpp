@@ -2270,39 +2270,85 @@ __global__ __launch_bounds__(256) void k_send(Dev d, int do_bt) {
 // the round's owner phase: packet entries KG (ping) and KG + 1 (ack), registered in the
 // receivers' inboxes like send_host's packets (unplanned path: the receiver's filter at the
 // sender, a locked receiver's records unfiltered to its pipeline). A team of T lanes per host.
-GXD bool probe_tick_of(const Dev &d, uint32_t u) {
+//
+// Sharded engines: a ping or ack to a host of another shard stays in the sender's message entry and
+// travels like a gossip packet (ob_dest; filtered on arrival, k_inbox_unpack). In a round that packs
+// the planned exchange itself (Dev::ob_buf) the team writes the packet straight into a slot of the
+// send buffer, claimed from the counters k_send claims from; k_xplan counted exactly these slots
+// (the predicates below at the planned round), so k_send's closing check covers them.
+GXD bool probe_tick_at(const Dev &d, int64_t round, uint32_t u) {
   const uint32_t P = d.p.fd_probe_rounds;
-  return (uint64_t)d.round % P == rng4(d.p.seed, ST_FD_PHASE, u, 0, 0) % P;
+  return (uint64_t)round % P == rng4(d.p.seed, ST_FD_PHASE, u, 0, 0) % P;
+}
+GXD bool probe_tick_of(const Dev &d, uint32_t u) { return probe_tick_at(d, d.round, u); }
+// One slot of destination shard g's region of the planned send buffer for every lane that asks for
+// one (g < d.G), or GX_NOSLOT. Called by whole waves: the wave's claims for a shard are one atomic,
+// as in send_planned.
+GXD uint32_t ob_claim_wave(const Dev &d, uint32_t g) {
+  const uint32_t lane = threadIdx.x & 63;
+  uint32_t slot = GX_NOSLOT;
+  unsigned long long pend = __ballot(g < d.G);
+  while (pend) {  // wave-uniform: one pass per destination shard
+    const int src = __builtin_ctzll(pend);
+    const uint32_t gs = (uint32_t)__shfl((int)g, src, 64);
+    const unsigned long long m = __ballot(g == gs);
+    uint32_t base = 0;
+    if ((int)lane == src) base = atomicAdd(&d.ob_claim[gs], (uint32_t)__popcll(m));
+    base = (uint32_t)__shfl((int)base, src, 64);
+    if (g == gs) {
+      const uint32_t at = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+      uint32_t st = 0;
+      for (uint32_t x = 0; x < gs; x++) st += d.ob_cnt[x];
+      if (at < d.ob_cnt[gs]) slot = st + at;
+      else atomicOr(&d.work_cnt[GX_WC_ERR], GX_ERR_INBOX);  // past the plan's bound (cannot happen)
+    }
+    pend &= ~m;
+  }
+  return slot;
 }
 template <int T>
 __global__ __launch_bounds__(256) void k_probe(Dev d) {
   Acc a;
   const uint32_t idx = blockIdx.x * (256 / T) + threadIdx.x / T, lane = threadIdx.x & (T - 1);
+  const uint32_t u = d.lo + idx;
   unsigned lost = 0;
   unsigned long long kb = 0;
+  // the ping (0): to u's image, when u probes this round; the ack (1): to the preimage, when its
+  // ping reached u
+  uint32_t peer[2] = {0u, 0u}, osl[2] = {GX_NOSLOT, GX_NOSLOT}, cross[2] = {0u, 0u};
+  bool act[2] = {false, false};
+  if (idx < d.Hl && !departed(d, u)) {
+    const uint64_t key = rng4(d.p.seed, ST_PROBE, (uint64_t)d.round, 0, 0);
+    if (probe_tick_of(d, u)) {
+      peer[0] = feistel_perm(key, u, d.H);
+      act[0] = peer[0] != u;
+    }
+    peer[1] = feistel_inv(key, u, d.H);
+    act[1] = peer[1] != u && !departed(d, peer[1]) && probe_tick_of(d, peer[1]) && reach(d, peer[1], u);
+  }
+  if (d.ob_buf) {  // (wave-uniform) the slots k_xplan counted: a packet that reaches a host of another shard
+#pragma unroll
+    for (int c = 0; c < 2; c++) {
+      const bool want = lane == 0 && act[c] && reach(d, u, peer[c]) && peer[c] - d.lo >= d.Hl;
+      osl[c] = ob_claim_wave(d, want ? shard_of_d(d, peer[c]) : d.G);
+      osl[c] = (uint32_t)__shfl((int)osl[c], 0, T);
+    }
+  }
   if (idx < d.Hl) {
-    const uint32_t u = d.lo + idx, cap = d.p.packet_cap;
+    const uint32_t cap = d.p.packet_cap;
     gx_host_state *h = &d.hs[idx];
     gx_host_state hs = *h;
-    const uint64_t key = rng4(d.p.seed, ST_PROBE, (uint64_t)d.round, 0, 0);
+#pragma unroll
     for (uint32_t c = 0; c < 2; c++) {
       const size_t x = (size_t)idx * d.KE + d.KG + c;
       if (lane == 0) {
         d.msg_len[x] = 0;
         d.msg_key[x] = u * d.KE + d.KG + c;
       }
-      if (departed(d, u)) continue;
-      uint32_t peer;
-      if (c == 0) {  // the ping: u's image, when u probes this round
-        if (!probe_tick_of(d, u)) continue;
-        peer = feistel_perm(key, u, d.H);
-        if (peer == u) continue;
-      } else {  // the ack: to the preimage, when its ping reached u
-        peer = feistel_inv(key, u, d.H);
-        if (peer == u || departed(d, peer) || !probe_tick_of(d, peer) || !reach(d, peer, u)) continue;
-      }
-      const bool ok = reach(d, u, peer), local = peer - d.lo < d.Hl;
-      uint32_t pos = lane == 0 && ok && local ? inbox_claim(d, peer - d.lo) : 0xffffffffu;
+      if (!act[c]) continue;
+      const uint32_t pr = peer[c];
+      const bool ok = reach(d, u, pr), local = pr - d.lo < d.Hl;
+      uint32_t pos = lane == 0 && ok && local ? inbox_claim(d, pr - d.lo) : 0xffffffffu;
       pos = (uint32_t)__shfl((int)pos, 0, T);
       uint32_t lim = d.p.limit_bytes;
       bool call = true;
@@ -2311,24 +2357,29 @@ __global__ __launch_bounds__(256) void k_probe(Dev d) {
         lim = lim > used ? lim - used : 0;
         call = lim > d.p.overhead_bytes;
       }
-      grec *pk = pos < d.DR ? &d.in_rec[((size_t)(peer - d.lo) * d.DR + pos) * cap] : &d.msg[x * cap];
-      const bool rlk = pos != 0xffffffffu && host_locked(d, peer);
+      grec *pk = pos < d.DR ? &d.in_rec[((size_t)(pr - d.lo) * d.DR + pos) * cap] : &d.msg[x * cap];
+      if (osl[c] != GX_NOSLOT) pk = reinterpret_cast<grec *>(ob_slot_hdr(d, osl[c]) + 4);
+      const bool rlk = pos != 0xffffffffu && host_locked(d, pr);
       const bool filt = d.sfilt && pos != 0xffffffffu && !(rlk && d.p.lock_model);
       uint32_t l = 0;
       if (call)
         l = get_broadcasts_team<T>(d, a, u, hs, cap, pk, lim, d.p.overhead_bytes, nullptr,
-                                   filt ? &d.view[(size_t)(peer - d.lo) * d.R] : nullptr, peer - d.lo);
+                                   filt ? &d.view[(size_t)(pr - d.lo) * d.R] : nullptr, pr - d.lo);
       if (rlk && l && lane == 0) {
         a.locked = true;
-        if (d.p.lock_model) flag_live(d, peer - d.lo, l);
+        if (d.p.lock_model) flag_live(d, pr - d.lo, l);
         else a.c[C_LOCKED_MERGES] += l;
       }
       if (lane == 0) {
         kb += 16 + 32ull * l + (filt ? 8ull * l : 0);
         d.msg_len[x] = ok ? l : 0;
         lost += l && !ok;
-        d.msg_dst[x] = peer;
-        if (pos != 0xffffffffu) inbox_header(d, peer - d.lo, pos, u * d.KE + d.KG + c, (uint32_t)x, l);
+        d.msg_dst[x] = pr;
+        cross[c] = l && ok && !local;
+        if (pos != 0xffffffffu) inbox_header(d, pr - d.lo, pos, u * d.KE + d.KG + c, (uint32_t)x, l);
+        if (osl[c] != GX_NOSLOT)  // the slot header (pack_slot's), or an empty slot (the receiver skips it)
+          *reinterpret_cast<uint4 *>(ob_slot_hdr(d, osl[c])) =
+              l ? make_uint4(u * d.KE + d.KG + c, pr, l, 0u) : make_uint4(GX_SLOT_EMPTY, 0u, 0u, 0u);
       }
     }
     if (lane == 0) *h = hs;
@@ -2337,6 +2388,13 @@ __global__ __launch_bounds__(256) void k_probe(Dev d) {
   if (lost) ctr_atomic(d, C_LOST, lost);
   kb = wave_sum(kb);
   if ((threadIdx.x & 63) == 0) kbytes(d, GX_K_SEND, kb, 0);
+  if (d.probe_x) {  // (sharded engines) gx_probe_cross: non-empty pings and acks to hosts of other shards
+#pragma unroll
+    for (int c = 0; c < 2; c++) {
+      const unsigned long long n = wave_sum((unsigned long long)cross[c]);
+      if ((threadIdx.x & 63) == 0 && n) atomicAdd(&d.probe_x[c], n);
+    }
+  }
 }
 
 // ============================================================== phase 4: gather-then-merge ==
@@ -4992,16 +5050,29 @@ __global__ __launch_bounds__(256) void k_xplan(Dev d, int64_t r0, uint32_t *cnt)
   const uint32_t u = blockIdx.x * blockDim.x + threadIdx.x, rr = blockIdx.y;
   if (u >= d.H) return;
   const int64_t round = r0 + rr;
+  const bool part = round >= d.p.partition_start && round < d.p.partition_end;
+  const uint32_t su = shard_of_d(d, u);
+  if (d.p.probe_piggyback) {  // k_probe's packets to other shards, by its predicates at that round
+    const uint64_t key = rng4(d.p.seed, ST_PROBE, (uint64_t)round, 0, 0);
+    const uint32_t half = d.H / 2;
+    if (probe_tick_at(d, round, u)) {  // u's ping reaches its image
+      const uint32_t p = feistel_perm(key, u, d.H), sp = shard_of_d(d, p);
+      if (p != u && !(part && (u < half) != (p < half)) && sp != su) atomicAdd(&cnt[((size_t)rr * d.G + su) * d.G + sp], 1u);
+    }
+    const uint32_t v = feistel_inv(key, u, d.H), sv = shard_of_d(d, v);  // u's ack to the host whose ping reached it
+    if (v != u && sv != su && !(part && (u < half) != (v < half)) && probe_tick_at(d, round, v))
+      atomicAdd(&cnt[((size_t)rr * d.G + su) * d.G + sv], 1u);
+  }
   // sample_peers of that round (its partition state)
   uint32_t base = 0, m = d.H;
-  if (round >= d.p.partition_start && round < d.p.partition_end) {
+  if (part) {
     const uint32_t half = d.H / 2;
     base = u < half ? 0 : half;
     m = u < half ? half : d.H - half;
   }
   if (m < 2) return;
   const uint64_t h3 = mix64(mix64(mix64(d.p.seed ^ ((uint64_t)ST_PEER * 0xD1B54A32D192ED03ull)) ^ (uint64_t)round) ^ u);
-  const uint32_t want = d.K < m - 1 ? d.K : m - 1, su = shard_of_d(d, u);
+  const uint32_t want = d.K < m - 1 ? d.K : m - 1;
   uint32_t peers[16], c = 0;
   for (uint32_t at = 0; c < want && at < 64u * d.K; at++) {
     const uint32_t ix = unif(mix64(h3 ^ at), m - 1), self = u - base;

@@ -147,11 +147,13 @@ class ShardRounds:
     def _planned_bufs(self) -> List[torch.Tensor]:
         """Each held shard's send buffer of the planned exchange, allocated once at its bound (k_send
         writes the slots straight into it, before the round's counts reach the host: a shard sends at
-        most fanout packet slots per host, gx.h gx_exchange_plan); the plan matrix comes with them."""
+        most fanout * GossipMessages packet slots per host, and with probe_piggyback the host's ping
+        and ack, gx.h gx_exchange_plan); the plan matrix comes with them."""
         if self._pb is None:
             p = self.shards[0].e.params
             slot = 16 + 16 * p.packet_cap
-            self._pb = [torch.empty((e.hi - e.lo) * p.fanout * slot, dtype=torch.uint8, device=self.device)
+            per_host = p.fanout * max(1, p.gossip_messages) + (2 if p.probe_piggyback else 0)
+            self._pb = [torch.empty((e.hi - e.lo) * per_host * slot, dtype=torch.uint8, device=self.device)
                         for e in self.engines]
             self._plan = np.zeros((self.G, self.G), dtype=np.uint64)  # m[src][dst], as gx_exchange_plan fills it
         return self._pb
@@ -207,6 +209,11 @@ class ShardRounds:
         if not self._arbitrate:
             return dict.fromkeys(keys, 0)
         return dict(zip(keys, map(sum, zip(*(e.ae_ro_counts() for e in self.engines)))))
+
+    def probe_cross(self):
+        """probe_piggyback: (pings, acks) with records that this process's shards have sent to hosts
+        of other shards since they were made (the HIP engine's gx_probe_cross; waits for the device)."""
+        return tuple(map(sum, zip(*(e.probe_cross() for e in self.engines))))
 
     def _ae_chain(self):
         """One run of the push-pull chain over the pairs the engines plan (the round's matching, or
