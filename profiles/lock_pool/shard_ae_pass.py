@@ -7,10 +7,12 @@ k_ae_want launches, the fold, G k_ae_claim_set launches and the local k_ae_rox).
 the arbitration, and the read-locked exchanges the round carried (oracle-free: the shards' counters).
 
     python profiles/lock_pool/shard_ae_pass.py [--G 8] [--hosts 4096] [--services 16] [--rounds 40]
+    python profiles/lock_pool/shard_ae_pass.py --libs parent.so sidecar_amd/libgx.so --reps 4
 """
 import argparse
 import json
 import os
+import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -64,15 +66,36 @@ def main():
     ap.add_argument("--hosts", type=int, default=4096)
     ap.add_argument("--services", type=int, default=16)
     ap.add_argument("--rounds", type=int, default=40)
+    ap.add_argument("--libs", nargs="+", default=None, help="builds of the engine to alternate (A/B), with --reps")
+    ap.add_argument("--reps", type=int, default=4)
     a = ap.parse_args()
     import torch
     torch.cuda.init()
-    from sidecar_amd.abi import INIT_OWN, load_product
-    lib = load_product()
+    from sidecar_amd.abi import INIT_OWN, load_library, load_product
     kw = dict(n_hosts=a.hosts, n_services=a.services, fanout=1, packet_cap=1, init_mode=INIT_OWN, churn_ppm=100000,
               alive_interval_rounds=2, tombstone_interval_rounds=7, ae_period_rounds=1, queue_cap=4096, storm_round=5)
-    out = {"G": a.G, "hosts": a.hosts, "services": a.services, "runs": [run(lib, a.G, kw, a.rounds, lr) for lr in (0, 1)]}
-    print(json.dumps(out), flush=True)
+    if not a.libs:
+        lib = load_product()
+        out = {"G": a.G, "hosts": a.hosts, "services": a.services,
+               "runs": [run(lib, a.G, kw, a.rounds, lr) for lr in (0, 1)]}
+        print(json.dumps(out), flush=True)
+        return
+    # A/B: the builds in one process, alternating; per (rep, build, lock_readers) the median pass over
+    # the rounds that ran the chain, then per build the median and spread (max - min) of those medians
+    libs = [(p, load_library(p)) for p in a.libs]
+    med = {p: {0: [], 1: []} for p, _ in libs}
+    for rep in range(a.reps):
+        for p, lib in libs:
+            for lr in (0, 1):
+                r = run(lib, a.G, kw, a.rounds, lr)
+                m = statistics.median(x["pass_us"] for x in r["rounds"])
+                med[p][lr].append(m)
+                print(json.dumps({"rep": rep, "lib": p, "G": a.G, "hosts": a.hosts, "services": a.services,
+                                  "lock_readers": lr, "median_pass_us": m, "skipped": r["skipped"],
+                                  "stats": r["stats"]}), flush=True)
+    print(json.dumps({"summary": {p: {f"lock_readers_{lr}": {"rep_medians_us": v, "median_us": statistics.median(v),
+                                                             "spread_us": round(max(v) - min(v), 1)}
+                                      for lr, v in by.items()} for p, by in med.items()}}), flush=True)
 
 
 if __name__ == "__main__":

@@ -140,6 +140,11 @@ static int dbuf(DevBuf &b, size_t bytes, void **out, size_t min_cap = 1 << 16) {
 // are 250 us of queued work at cfg 5; the shortest quiet stretches of the test schedules are 10.
 #define GX_QUIET_SLOTS 4
 
+// The calls of a sharded engine's push-pull chain that later calls of the same step build on
+// (gx_engine::AeChain::done): gx_ae_bytes, gx_ae_merge_local, gx_ae_delta_bytes, gx_ae_return_bytes,
+// gx_ae_claim_set.
+enum AeCall : uint32_t { AE_PLANNED = 1, AE_LOCAL = 2, AE_DELTA = 4, AE_RET = 8, AE_CLAIM = 16 };
+
 struct gx_engine {
   Dev d{};
   DevMem mem;  // every device buffer that lives as long as the engine
@@ -203,7 +208,6 @@ struct gx_engine {
   uint64_t *fd_rsnap;                // [pairs][H] partner member lists received with the digests
   int32_t *ae_prow;
   uint8_t *ae_pcount;
-  uint32_t n_plan, n_pack, n_plan_rows;
   // push-pull digests / delta (per cross pair k, in pack order = receive order)
   uint32_t nblk, nmw;
   ulonglong2 *ae_dig;  // [Hl][nblk] own digests
@@ -222,14 +226,17 @@ struct gx_engine {
   // the driver's counters (gx_ae_ro_counts)
   uint8_t *ae_rov;             // [pairs] 1: this side is read-locked | 2: the partner is; 0: another verdict
   unsigned long long *ro_xc;   // [3]
-  int64_t ae_claim_round = -1; // the step gx_ae_claim_set last ran for (ae_step)
-  std::vector<uint32_t> pack_gstart;  // pack index range per destination shard
-  std::vector<uint64_t> delta_off_h;
-  uint64_t delta_total, lead_in_total, ret_total;
-  // the chain's guards: the step (ae_step: round and batch) each call last completed for
-  int64_t ae_delta_round = -1, ae_ret_round = -1;
-  int64_t ae_planned_round = -1;
-  int64_t ae_local_round = -1;
+  // The push-pull chain's host state (gx_ae_chain_host.hpp), all of one step (ae_step: the round, in
+  // GX_PP_INITIATE the batch too): what gx_ae_bytes planned, the sizes the later calls check their
+  // buffers against, and which calls have completed for the step (AeCall bits; ae_done, ae_mark).
+  struct AeChain {
+    int64_t step = -1;
+    uint32_t done;
+    uint32_t n_plan, n_pack;  // planned pairs (ae_pa, ae_pb): the n_pack cross pairs in pack order, then the local ones
+    std::vector<uint32_t> gstart;          // pack index range per destination shard
+    std::vector<uint64_t> lead_off;        // [2][n_pack] lead message offsets, out and in the inbox (ae_off's first half)
+    uint64_t lead_total, lead_in_total, ret_total;  // bytes of the lead messages out, of those in, of the return out
+  } chain;
   // listeners: host-side channels fed from the per-view device event logs
   struct Listener {
     uint32_t view, id, cap;
@@ -775,6 +782,26 @@ static bool pp_initiates(const Dev &d, uint32_t i) {
   if (!d.p.push_pull_stagger) return true;
   return (uint64_t)d.round % d.p.ae_period_rounds == rng4(d.p.seed, ST_PP_PHASE, i, 0, 0) % d.p.ae_period_rounds;
 }
+// The round's matching (GX_PP_MATCHING): the hosts [base[i], base[i] + len[i]) of each group (one, or
+// the two sides of a pair split) are paired off by a Feistel permutation keyed key0 / key1, n0 pairs
+// in group 0 and np in all, as k_ae and k_ae_pairs draw them.
+struct AeMatching {
+  uint32_t base[2], len[2];
+  uint64_t key0, key1;
+  uint32_t n0, np;
+};
+static AeMatching ae_matching(const Dev &d) {
+  AeMatching m;
+  m.base[0] = 0;
+  m.base[1] = d.H / 2;
+  m.len[0] = d.pair_split ? d.H / 2 : d.H;
+  m.len[1] = d.pair_split ? d.H - d.H / 2 : 0;
+  m.key0 = rng4(d.p.seed, ST_AE, (uint64_t)d.round, m.base[0], 0);
+  m.key1 = m.len[1] ? rng4(d.p.seed, ST_AE, (uint64_t)d.round, m.base[1], 0) : 0;
+  m.n0 = m.len[0] / 2;
+  m.np = m.n0 + m.len[1] / 2;
+  return m;
+}
 
 // GX_PP_INITIATE: every live host starts one exchange with a partner drawn at random on its side;
 // the exchanges run in initiator order, in batches of exchanges with no host in common (an exchange
@@ -893,17 +920,9 @@ static int ae_whole_impl(gx_engine *e, bool quiet) {
     int rc = ae_initiate(e);
     if (rc) return rc;
   } else if (ae_round(e)) {
-    uint32_t np;
-    uint64_t key0, key1 = 0;
-    if (d.pair_split) {
-      uint32_t m0 = d.H / 2, m1 = d.H - m0;
-      np = m0 / 2 + m1 / 2;
-      key0 = rng4(d.p.seed, ST_AE, (uint64_t)d.round, 0, 0);
-      key1 = rng4(d.p.seed, ST_AE, (uint64_t)d.round, m0, 0);
-    } else {
-      np = d.H / 2;
-      key0 = rng4(d.p.seed, ST_AE, (uint64_t)d.round, 0, 0);
-    }
+    const AeMatching m = ae_matching(d);
+    const uint32_t np = m.np;
+    const uint64_t key0 = m.key0, key1 = m.key1;
     if (np && quiet) {  // every host holds the lock: each pair fails on it, the round is only its counts
       LaunchTimer t(e, GX_K_AE);
       k_ae_locked_note<<<1, 64, 0, s>>>(d, np, 1u);
@@ -2077,10 +2096,6 @@ static uint32_t shard_of(const Dev &d, uint32_t v) {  // shard g owns [floor(g H
 static size_t slot_bytes(const Dev &d) {
   return 16 + 16ull * d.p.packet_cap + (d.p.fd_enable ? 16ull * d.p.fd_msg_cap : 0);
 }
-static size_t dig_bytes(const gx_engine *e) { return dig_stride(e->d, e->nblk); }
-// the sharded push-pull's lead and return kernels with the offsets up front, a wave per block
-// (profiles/ab_shard_ae.sh), while a row's digest blocks fit their LDS tables
-static bool ae_wave_blocks(const gx_engine *e) { return e->nblk <= XS_MAXB; }
 
 int gx_round_send(gx_engine *e) {
   if (!e) return GX_EINVAL;
@@ -2271,501 +2286,6 @@ int gx_round_merge(gx_engine *e) {
   quiet_invalidate(e);
   int rc = round_merge_impl(e);
   return rc ? rc : phase_done(e);
-}
-
-// Push-pull plan of this round (host side): global pairs t -> (a, b); local pairs, rows to send
-// (grouped by destination shard, ascending t) and rows to receive (by source shard, ascending t).
-static int ae_plan(gx_engine *e, uint64_t *bytes) {
-  Dev &d = e->d;
-  set_round_fields(e);
-  std::vector<uint32_t> pa, pb, pt;  // pt: each pair's index in the round's list (the messages' pair index)
-  if (d.p.push_pull_mode == GX_PP_INITIATE) {
-    // the batch at the cursor (ae_step_due): its exchanges, named by their place in initiator order
-    pp_schedule(e);
-    const size_t n = e->pp_idx.size(), lo = e->pp_off[e->pp_cursor], hi = e->pp_off[e->pp_cursor + 1];
-    if (hi - lo > d.H / 2) return GX_EINVAL;  // hosts of a batch are disjoint: the pair buffers hold H / 2 + 1
-    pa.assign(e->pp_host.begin() + lo, e->pp_host.begin() + hi);
-    pb.assign(e->pp_host.begin() + n + lo, e->pp_host.begin() + n + hi);
-    pt.assign(e->pp_idx.begin() + lo, e->pp_idx.begin() + hi);
-    int rc = sync_check(e);  // the batch before (its launches read the plan rewritten below) is done
-    if (rc) return rc;
-  } else {
-    uint32_t groups[2][2];
-    int ng;
-    if (d.pair_split) {
-      groups[0][0] = 0; groups[0][1] = d.H / 2;
-      groups[1][0] = d.H / 2; groups[1][1] = d.H - d.H / 2;
-      ng = 2;
-    } else {
-      groups[0][0] = 0; groups[0][1] = d.H;
-      ng = 1;
-    }
-    // the pair schedule (Feistel permutations, as k_ae draws it) on the device, read back once
-    uint32_t n0 = groups[0][1] / 2, n1 = ng > 1 ? groups[1][1] / 2 : 0, np = n0 + n1;
-    uint64_t key0 = rng4(d.p.seed, ST_AE, (uint64_t)d.round, groups[0][0], 0);
-    uint64_t key1 = ng > 1 ? rng4(d.p.seed, ST_AE, (uint64_t)d.round, groups[1][0], 0) : 0;
-    pa.resize(np);
-    pb.resize(np);
-    pt.resize(np);
-    std::iota(pt.begin(), pt.end(), 0u);
-    if (np) {
-      k_ae_pairs<<<(np + 255) / 256, 256, 0, e->stream>>>(groups[0][0], groups[0][1], key0, groups[1][0],
-                                                           ng > 1 ? groups[1][1] : 0, key1, n0, np, e->ae_pa, e->ae_pb);
-      HIPCHK(hipMemcpyAsync(pa.data(), e->ae_pa, 4ull * np, hipMemcpyDeviceToHost, e->stream));
-      HIPCHK(hipMemcpyAsync(pb.data(), e->ae_pb, 4ull * np, hipMemcpyDeviceToHost, e->stream));
-      int rc = sync_check(e);
-      if (rc) return rc;
-    }
-  }
-  // a pair with a crashed member does not run (both shards skip it alike; pair indices unchanged)
-  std::vector<uint8_t> runs(pa.size(), 1);
-  if (d.departures)
-    for (size_t t = 0; t < pa.size(); t++)
-      runs[t] = !departed_at(d.p, d.round, pa[t]) && !departed_at(d.p, d.round, pb[t]);
-  // one pass over the pairs: cross pairs bucketed by the partner's shard (messages go out and
-  // come in grouped by shard, ascending t, so cross pair k has the same index both ways), then
-  // the pairs with both hosts here
-  std::vector<std::vector<uint32_t>> by_g(d.G);
-  std::vector<uint32_t> local_t;
-  for (size_t t = 0; t < pa.size(); t++) {
-    if (!runs[t]) continue;
-    bool la = own(e, pa[t]), lb = own(e, pb[t]);
-    if (la && lb) local_t.push_back((uint32_t)t);
-    else if (la != lb) by_g[shard_of(d, la ? pb[t] : pa[t])].push_back((uint32_t)t);
-  }
-  std::vector<uint32_t> plan_a, plan_b, pack_host, pack_t, pack_other;
-  std::vector<uint8_t> pack_first;
-  std::vector<int32_t> plan_row;
-  std::vector<uint8_t> plan_cnt;
-  for (uint32_t g = 0; g < d.G; g++) bytes[g] = 0;
-  e->pack_gstart.assign(d.G + 1, 0);
-  int32_t row = 0;
-  for (uint32_t g = 0; g < d.G; g++) {
-    e->pack_gstart[g] = (uint32_t)pack_host.size();
-    for (uint32_t t : by_g[g]) {
-      bool la = own(e, pa[t]);
-      uint32_t mine = la ? pa[t] : pb[t], other = la ? pb[t] : pa[t];
-      pack_host.push_back(mine);
-      pack_t.push_back(pt[t]);
-      pack_other.push_back(other);
-      pack_first.push_back(la ? 1 : 0);
-      bytes[g] += dig_bytes(e);
-      plan_a.push_back(mine);
-      plan_b.push_back(other);
-      plan_row.push_back(row++);
-      plan_cnt.push_back(la ? 1 : 0);
-    }
-  }
-  e->pack_gstart[d.G] = (uint32_t)pack_host.size();
-  for (uint32_t t : local_t) {
-    plan_a.push_back(pa[t]);
-    plan_b.push_back(pb[t]);
-    plan_row.push_back(-1);
-    plan_cnt.push_back(0);
-  }
-  e->n_plan = (uint32_t)plan_a.size();
-  e->n_plan_rows = (uint32_t)row;
-  e->n_pack = (uint32_t)pack_host.size();
-  if (e->n_plan) {
-    HIPCHK(hipMemcpy(e->ae_pa, plan_a.data(), 4 * e->n_plan, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(e->ae_pb, plan_b.data(), 4 * e->n_plan, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(e->ae_prow, plan_row.data(), 4 * e->n_plan, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(e->ae_pcount, plan_cnt.data(), e->n_plan, hipMemcpyHostToDevice));
-  }
-  if (e->n_pack) {
-    HIPCHK(hipMemcpy(e->ae_pack_host, pack_host.data(), 4 * e->n_pack, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(e->ae_pack_t, pack_t.data(), 4 * e->n_pack, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(e->ae_pack_other, pack_other.data(), 4 * e->n_pack, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(e->ae_pack_first, pack_first.data(), e->n_pack, hipMemcpyHostToDevice));
-    HIPCHK(hipMemsetAsync(e->ae_skip, 0, e->n_pack, e->stream));
-  }
-  if (pp_state(d)) k_fd_snap<<<2048, 256, 0, e->stream>>>(d);  // round-start member lists (pushPull)
-  e->ae_planned_round = ae_step(e);
-  return GX_OK;
-}
-
-int gx_ae_bytes(gx_engine *e, uint64_t *bytes) {
-  if (!e || !bytes) return GX_EINVAL;
-  HIPCHK(hipSetDevice(e->device));
-  for (uint32_t g = 0; g < e->d.G; g++) bytes[g] = 0;
-  e->n_plan = e->n_pack = e->n_plan_rows = 0;
-  e->ae_planned_round = -1;
-  if (!ae_step_due(e)) return GX_OK;
-  return ae_plan(e, bytes);
-}
-
-int gx_ae_pack(gx_engine *e, void *buf, uint64_t cap) {
-  if (!e || (cap && !buf)) return GX_EINVAL;
-  if (!e->n_pack) return GX_OK;
-  if (e->ae_planned_round != ae_step(e) || cap < e->n_pack * dig_bytes(e)) return GX_EINVAL;
-  HIPCHK(hipSetDevice(e->device));
-  with_flags(vec_of(e), e->d.p.lock_readers != 0, [&](auto V, auto RO) {
-    k_ae_digest<V(), RO()><<<e->n_pack, 256, 0, e->stream>>>(e->d, e->ae_pack_host, e->ae_pack_t, e->ae_pack_other,
-                                                              e->ae_pack_first, (uint8_t *)buf, e->ae_dig, e->nblk,
-                                                              e->ae_bcnt);
-  });
-  return phase_done(e);
-}
-
-// Received digests -> differing blocks and who leads each; lead message sizes per shard, and the
-// offsets of this side's lead messages and of the partner's in the lead inbox.
-int gx_ae_delta_bytes(gx_engine *e, const void *digests, uint64_t bytes, uint64_t *out) {
-  if (!e || !out || (bytes && !digests)) return GX_EINVAL;
-  HIPCHK(hipSetDevice(e->device));
-  Dev &d = e->d;
-  for (uint32_t g = 0; g < d.G; g++) out[g] = 0;
-  e->ae_delta_round = e->ae_ret_round = -1;
-  e->delta_total = e->lead_in_total = 0;
-  if (!ae_step_due(e)) return bytes ? GX_EINVAL : GX_OK;
-  if (e->ae_planned_round != ae_step(e) || bytes != e->n_pack * dig_bytes(e)) return GX_EINVAL;
-  const uint32_t np = e->n_pack;
-  std::vector<uint64_t> sz(2 * (size_t)np);
-  if (np) {
-    HIPCHK(hipMemsetAsync(e->ae_err, 0, sizeof(uint32_t), e->stream));
-    if (d.p.lock_readers)  // the read-locked verdicts as well (gx.h lock_readers)
-      k_ae_mask<true><<<np, 256, 0, e->stream>>>(d, (const uint8_t *)digests, e->ae_dig, e->ae_pack_t, e->ae_pack_host,
-                                                 e->ae_pack_other, e->ae_pack_first, e->nblk, e->nmw, e->ae_mask,
-                                                 e->ae_fmask, e->ae_lt, e->ae_cnt, e->ae_nfol, e->ae_sz, e->ae_sz + np,
-                                                 e->ae_err, e->ae_skip, e->ae_rov, e->ro_xc);
-    else
-      k_ae_mask<><<<np, 256, 0, e->stream>>>(d, (const uint8_t *)digests, e->ae_dig, e->ae_pack_t, e->ae_pack_host,
-                                             e->ae_pack_other, e->ae_pack_first, e->nblk, e->nmw, e->ae_mask,
-                                             e->ae_fmask, e->ae_lt, e->ae_cnt, e->ae_nfol, e->ae_sz, e->ae_sz + np,
-                                             e->ae_err, e->ae_skip);
-    if (pp_state(d))  // the partners' member lists ride with their digests
-      k_fd_rsnap<<<1024, 256, 0, e->stream>>>(d, (const uint8_t *)digests, dig_bytes(e), e->nblk, np, e->fd_rsnap);
-    uint32_t err = 0;
-    HIPCHK(hipMemcpyAsync(&err, e->ae_err, sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipMemcpyAsync(sz.data(), e->ae_sz, sizeof(uint64_t) * 2 * np, hipMemcpyDeviceToHost, e->stream));
-    int rc = sync_main(e);
-    if (rc) return rc;
-    if (err) return GX_EINVAL;  // digests of another pair or another row size
-  }
-  e->delta_off_h.assign(2 * (size_t)np, 0);
-  uint64_t o = 0, oi = 0;
-  for (uint32_t g = 0; g < d.G; g++)
-    for (uint32_t k = e->pack_gstart[g]; k < e->pack_gstart[g + 1]; k++) {
-      e->delta_off_h[k] = o;
-      e->delta_off_h[np + k] = oi;
-      out[g] += sz[k];
-      o += sz[k];
-      oi += sz[np + k];
-    }
-  e->delta_total = o;
-  e->lead_in_total = oi;
-  if (np) HIPCHK(hipMemcpy(e->ae_off, e->delta_off_h.data(), sizeof(uint64_t) * 2 * np, hipMemcpyHostToDevice));
-  e->ae_delta_round = ae_step(e);
-  return GX_OK;
-}
-
-int gx_ae_delta_pack(gx_engine *e, void *buf, uint64_t cap) {
-  if (!e || (cap && !buf)) return GX_EINVAL;
-  if (!e->n_pack) return GX_OK;
-  if (e->ae_delta_round != ae_step(e) || cap < e->delta_total) return GX_EINVAL;
-  HIPCHK(hipSetDevice(e->device));
-  if (ae_wave_blocks(e))
-    k_ae_lead_pack_w<<<e->n_pack, 256, 0, e->stream>>>(e->d, e->ae_pack_host, e->ae_pack_t, e->ae_mask, e->ae_cnt,
-                                                        e->ae_off, e->nmw, (const ulonglong2 *)e->ae_dig, e->nblk,
-                                                        (uint8_t *)buf);
-  else
-    k_ae_lead_pack<<<e->n_pack, 256, 0, e->stream>>>(e->d, e->ae_pack_host, e->ae_pack_t, e->ae_mask, e->ae_cnt,
-                                                      e->ae_off, e->nmw, (uint8_t *)buf);
-  return phase_done(e);
-}
-
-// Received lead blocks -> return message sizes: per destination shard a u64 size table, then the
-// messages (gx.h "return").
-int gx_ae_return_bytes(gx_engine *e, const void *lead, uint64_t lead_bytes, uint64_t *out) {
-  if (!e || !out || (lead_bytes && !lead)) return GX_EINVAL;
-  HIPCHK(hipSetDevice(e->device));
-  Dev &d = e->d;
-  for (uint32_t g = 0; g < d.G; g++) out[g] = 0;
-  e->ae_ret_round = -1;
-  e->ret_total = 0;
-  const uint32_t np = e->n_pack;
-  if (!ae_step_due(e) || !np) return lead_bytes ? GX_EINVAL : GX_OK;
-  if (e->ae_delta_round != ae_step(e) || lead_bytes != e->lead_in_total) return GX_EINVAL;
-  if (ae_wave_blocks(e))
-    k_ae_ret_w<true><<<np, 256, 0, e->stream>>>(d, e->ae_pack_host, e->ae_pack_t, e->ae_fmask, e->ae_nfol, e->ae_lt,
-                                                (const uint8_t *)lead, e->ae_off + np, e->nblk, e->nmw,
-                                                e->ae_sz + 2 * np, nullptr, nullptr, nullptr, e->ae_retL);
-  else
-    k_ae_ret<true><<<np, 256, 0, e->stream>>>(d, e->ae_pack_host, e->ae_pack_t, e->ae_fmask, e->ae_nfol, e->ae_lt,
-                                              (const uint8_t *)lead, e->ae_off + np, e->nblk, e->nmw,
-                                              e->ae_sz + 2 * np, nullptr, nullptr, nullptr);
-  std::vector<uint64_t> rsz(np);
-  HIPCHK(hipMemcpyAsync(rsz.data(), e->ae_sz + 2 * np, sizeof(uint64_t) * np, hipMemcpyDeviceToHost, e->stream));
-  int rc = sync_main(e);
-  if (rc) return rc;
-  std::vector<uint64_t> off(2 * (size_t)np);  // message offsets, size-table entry offsets
-  uint64_t o = 0;
-  for (uint32_t g = 0; g < d.G; g++) {
-    uint32_t k0 = e->pack_gstart[g], k1 = e->pack_gstart[g + 1];
-    uint64_t seg = o;
-    o += 8ull * (k1 - k0);
-    for (uint32_t k = k0; k < k1; k++) {
-      off[np + k] = seg + 8ull * (k - k0);
-      off[k] = o;
-      o += rsz[k];
-    }
-    out[g] = o - seg;
-  }
-  e->ret_total = o;
-  HIPCHK(hipMemcpy(e->ae_off + 2 * np, off.data(), sizeof(uint64_t) * 2 * np, hipMemcpyHostToDevice));
-  e->ae_ret_round = ae_step(e);
-  return GX_OK;
-}
-
-int gx_ae_return_pack(gx_engine *e, const void *lead, uint64_t lead_bytes, void *buf, uint64_t cap) {
-  if (!e || (cap && !buf) || (lead_bytes && !lead)) return GX_EINVAL;
-  const uint32_t np = e->n_pack;
-  if (!np) return GX_OK;
-  if (e->ae_ret_round != ae_step(e) || cap < e->ret_total || lead_bytes != e->lead_in_total) return GX_EINVAL;
-  HIPCHK(hipSetDevice(e->device));
-  if (ae_wave_blocks(e))
-    k_ae_ret_w<false><<<np, 256, 0, e->stream>>>(e->d, e->ae_pack_host, e->ae_pack_t, e->ae_fmask, e->ae_nfol,
-                                                 e->ae_lt, (const uint8_t *)lead, e->ae_off + np, e->nblk, e->nmw,
-                                                 e->ae_sz + 2 * np, e->ae_off + 2 * np, e->ae_off + 3 * np,
-                                                 (uint8_t *)buf, e->ae_retL);
-  else
-    k_ae_ret<false><<<np, 256, 0, e->stream>>>(e->d, e->ae_pack_host, e->ae_pack_t, e->ae_fmask, e->ae_nfol, e->ae_lt,
-                                               (const uint8_t *)lead, e->ae_off + np, e->nblk, e->nmw,
-                                               e->ae_sz + 2 * np, e->ae_off + 2 * np, e->ae_off + 3 * np,
-                                               (uint8_t *)buf);
-  return phase_done(e);
-}
-
-// The cross pairs' inboxes and per-pair tables, as the kernels that rebuild a partner's row take them.
-static AeIn ae_in(const gx_engine *e, const void *lead, const void *ret) {
-  AeIn in;
-  in.lead = (const uint8_t *)lead;
-  in.ret = (const uint8_t *)ret;
-  in.ioff = e->ae_off + e->n_pack;
-  in.rioff = e->ae_rioff;
-  in.lmask = e->ae_mask;
-  in.fmask = e->ae_fmask;
-  in.lt = e->ae_lt;
-  in.nlead = e->ae_cnt;
-  in.bcnt = e->ae_bcnt;
-  in.nmw = e->nmw;
-  in.nblk = e->nblk;
-  return in;
-}
-// Launch the planned pairs [lo, hi) (received-row pairs first, then shard-local pairs).
-static void ae_plan_launch(gx_engine *e, uint32_t lo, uint32_t hi, const void *lead, const void *ret,
-                           hipStream_t st = nullptr) {
-  if (hi <= lo) return;
-  if (!st) st = e->stream;
-  set_round_fields(e);
-  LaunchTimer t(e, GX_K_AE, st);
-  const AeIn in = ae_in(e, lead, ret);
-  // fewer than 4 pairs per CU: per-block bandwidth decides (2 tiles in flight measured slower for
-  // the cross pairs of a post-heal round: 8.2 -> 9.3 ms at G = 2, H = 16384)
-  const bool small = hi - lo < 1024;
-  launch_ae_plan(e, small, hi - lo, st, e->ae_pa + lo, e->ae_pb + lo, e->ae_prow + lo, e->ae_pcount + lo, in, e->ae_skip);
-}
-
-// gx.h lock_readers: the pool rows of the cross pairs' admitted read-locked sides (k_ae_xdefer)
-static void ae_xdefer_launch(gx_engine *e, const void *lead) {
-  if (!e->n_pack) return;
-  set_round_fields(e);
-  LaunchTimer t(e, GX_K_AE);
-  const AeIn in = ae_in(e, lead, nullptr);
-  with_flag(vec_of(e), [&](auto V) {
-    k_ae_xdefer<V()><<<e->n_pack, 256, 0, e->stream>>>(e->d, e->ae_pack_host, e->ae_pack_first, e->ae_rov, in, e->ro_xc);
-  });
-}
-
-int gx_ae_merge_local(gx_engine *e) {
-  if (!e) return GX_EINVAL;
-  HIPCHK(hipSetDevice(e->device));
-  if (!ae_step_due(e) || e->ae_local_round == ae_step(e)) return GX_OK;
-  if (e->ae_planned_round != ae_step(e)) return GX_EINVAL;
-  // on the side stream, after the rows are packed: the exchange layer's collectives (ordered
-  // behind `stream`) run while these merges do; gx_ae_merge joins them back
-  HIPCHK(hipEventRecord(e->side_start, e->stream));
-  HIPCHK(hipStreamWaitEvent(e->side_stream, e->side_start, 0));
-  ae_plan_launch(e, e->n_plan_rows, e->n_plan, nullptr, nullptr, e->side_stream);
-  HIPCHK(hipEventRecord(e->side_done, e->side_stream));
-  e->side_pending = true;
-  HIPCHK(hipGetLastError());
-  e->ae_local_round = ae_step(e);
-  return GX_OK;
-}
-
-int gx_ae_merge(gx_engine *e, const void *lead, uint64_t lead_bytes, const void *ret, uint64_t ret_bytes) {
-  if (!e || (lead_bytes && !lead) || (ret_bytes && !ret)) return GX_EINVAL;
-  HIPCHK(hipSetDevice(e->device));
-  quiet_invalidate(e);
-  if (!ae_round(e)) return GX_OK;
-  if (e->d.G < 2) {
-    int rc = ae_whole_impl(e, false);
-    return rc ? rc : sync_check(e);
-  }
-  if (!ae_step_due(e)) return (lead_bytes || ret_bytes) ? GX_EINVAL : GX_OK;  // past the round's last batch
-  if (e->ae_planned_round != ae_step(e)) return GX_EINVAL;
-  const uint32_t np = e->n_pack;
-  if (np) {
-    if (e->ae_ret_round != ae_step(e) || lead_bytes != e->lead_in_total) return GX_EINVAL;
-    // the return inbox: per source shard a size table, then that shard's messages
-    std::vector<uint64_t> rio(np), tab;
-    uint64_t o = 0;
-    for (uint32_t g = 0; g < e->d.G; g++) {
-      uint32_t k0 = e->pack_gstart[g], k1 = e->pack_gstart[g + 1];
-      if (k1 == k0) continue;
-      if (o + 8ull * (k1 - k0) > ret_bytes) return GX_EINVAL;
-      tab.resize(k1 - k0);
-      HIPCHK(hipMemcpyAsync(tab.data(), (const uint8_t *)ret + o, 8ull * (k1 - k0), hipMemcpyDeviceToHost, e->stream));
-      HIPCHK(hipStreamSynchronize(e->stream));
-      o += 8ull * (k1 - k0);
-      for (uint32_t k = k0; k < k1; k++) {
-        rio[k] = o;
-        o += tab[k - k0];
-      }
-    }
-    if (o != ret_bytes) return GX_EINVAL;
-    HIPCHK(hipMemcpy(e->ae_rioff, rio.data(), sizeof(uint64_t) * np, hipMemcpyHostToDevice));
-  }
-  if (e->d.p.lock_readers) {  // the admitted read-locked sides of cross pairs keep their partners' rows
-    if (e->ae_claim_round != ae_step(e)) return GX_EINVAL;  // gx_ae_claim_want, gx_ae_claim_set come first
-    ae_xdefer_launch(e, lead);
-  }
-  bool local_done = e->ae_local_round == ae_step(e);
-  ae_plan_launch(e, 0, local_done ? e->n_plan_rows : e->n_plan, lead, ret);
-  if (pp_state(e->d) && e->n_plan) {  // pushPull's membership half, every planned pair
-    LaunchTimer t(e, GX_K_FD);
-    k_fd_pushpull_plan<<<2 * e->n_plan, 64, 0, e->stream>>>(e->d, e->ae_pa, e->ae_pb, e->ae_prow, e->ae_skip,
-                                                             e->fd_rsnap);
-  }
-  int jr = join_side(e);  // the next batch, and the next round's phases, see the local pairs merged
-  if (jr) return jr;
-  if (e->d.p.push_pull_mode == GX_PP_INITIATE) e->pp_cursor++;  // the chain's next run takes the next batch
-  return phase_done(e);
-}
-
-// gx.h lock_readers = 1 on a sharded engine (outside gx.h's declarations, described there with the
-// sharded rounds): the cluster-wide pool's arbitration, between gx_ae_delta_bytes and gx_ae_merge in
-// every run of the chain. gx_ae_claim_want writes lock_defer_slots int64 entries at `want` (device
-// memory): -1 for a slot one of this shard's hosts holds, else this shard's lowest claimant of the
-// slot in this run (the read-locked sides of its local and cross pairs), else 2^62. The caller takes
-// the minimum over all shards and hands it to gx_ae_claim_set, which admits the claimants named in
-// it, counts the others lost and runs the local read-locked exchanges (k_ae_rox). A run with nothing
-// planned on this shard still answers (held slots, no claimants) and sets nothing.
-static bool ae_claims_on(const gx_engine *e) { return e->d.G > 1 && e->d.p.lock_readers; }
-int gx_ae_claim_want(gx_engine *e, int64_t *want) {
-  if (!e || !want || !ae_claims_on(e)) return GX_EINVAL;
-  HIPCHK(hipSetDevice(e->device));
-  const bool due = ae_step_due(e);
-  if (due && (e->ae_planned_round != ae_step(e) || (e->n_pack && e->ae_delta_round != ae_step(e)))) return GX_EINVAL;
-  if (due && e->ae_local_round != ae_step(e)) {  // the local pairs' launch flags their read-locked exchanges
-    int rc = gx_ae_merge_local(e);
-    if (rc) return rc;
-  }
-  int jr = join_side(e);  // ro_flag is written
-  if (jr) return jr;
-  set_round_fields(e);
-  const uint32_t lo = due ? e->n_plan_rows : 0, nl = due ? e->n_plan - lo : 0, np = due ? e->n_pack : 0;
-  k_ae_want<<<1, 256, 0, e->stream>>>(e->d, e->ae_pa + lo, e->ae_pb + lo, nl, e->ae_pack_host, e->ae_rov, np,
-                                      (long long *)want);
-  return phase_done(e);
-}
-int gx_ae_claim_set(gx_engine *e, const int64_t *won) {
-  if (!e || !won || !ae_claims_on(e)) return GX_EINVAL;
-  HIPCHK(hipSetDevice(e->device));
-  if (!ae_step_due(e)) return GX_OK;
-  if (e->ae_planned_round != ae_step(e) || e->ae_local_round != ae_step(e) || e->side_pending) return GX_EINVAL;
-  set_round_fields(e);
-  const uint32_t lo = e->n_plan_rows, nl = e->n_plan - lo;
-  {
-    LaunchTimer t(e, GX_K_AE);
-    k_ae_claim_set<<<1, 256, 0, e->stream>>>(e->d, e->ae_pa + lo, e->ae_pb + lo, nl, e->ae_pack_host, e->ae_rov,
-                                             e->n_pack, (const long long *)won, e->ro_xc);
-    if (nl)  // the local read-locked exchanges, slots decided
-      with_flags(vec_of(e), ev_of(e), [&](auto V, auto E) {
-        k_ae_rox<V(), E()><<<ae_grid(nl, 1), 256, 0, e->stream>>>(e->d, e->ae_pa + lo, e->ae_pb + lo, 0, 0);
-      });
-  }
-  e->ae_claim_round = ae_step(e);
-  return phase_done(e);
-}
-// The driver's counters of the sharded read-locked exchanges, summed since gx_create: out[0] cross-
-// shard exchanges that ran with a read-locked side (counted by the shard of the pair's first host),
-// out[1] read-locked sides of cross pairs admitted to the pool, out[2] sides of this shard that lost
-// their merge to a host of another shard (the slot's holder, or a lower claimant). Waits for the device.
-int gx_ae_ro_counts(gx_engine *e, uint64_t *out) {
-  if (!e || !out || !ae_claims_on(e)) return GX_EINVAL;
-  HIPCHK(hipSetDevice(e->device));
-  HIPCHK(hipMemcpyAsync(out, e->ro_xc, sizeof(uint64_t) * 3, hipMemcpyDeviceToHost, e->stream));
-  return sync_check(e);
-}
-
-int gx_lock_census(gx_engine *e, uint32_t *unlocked) {
-  if (!e || !unlocked) return GX_EINVAL;
-  HIPCHK(hipSetDevice(e->device));
-  int rc = ensure_api(e, sizeof(uint32_t));
-  if (rc) return rc;
-  set_round_fields(e);
-  uint32_t *dv = (uint32_t *)e->api.p;
-  HIPCHK(hipMemsetAsync(dv, 0, sizeof(uint32_t), e->stream));
-  if (e->d.Hl) k_lock_census<<<nblk(e->d.Hl, 256), 256, 0, e->stream>>>(e->d, dv);
-  return read_back(e, dv, unlocked);
-}
-
-// A push-pull round in which every host of the cluster holds the lock (the caller's collective
-// census): every pair fails, so the round is only its counts, as the full exchange would make them
-// (gx_ae_bytes .. gx_ae_merge): ae_locked once per pair, by the shard of its first host.
-int gx_ae_skip_locked(gx_engine *e) {
-  if (!e) return GX_EINVAL;
-  Dev &d = e->d;
-  if (!ae_round(e)) return GX_OK;
-  // sharded engines only (one engine runs its push-pull itself; the pair buffers exist when G > 1)
-  // (nor with lock_readers: an exchange between read-locked hosts runs)
-  if (d.G < 2 || !e->ae_pa || !d.p.lock_model || d.departures || d.p.fd_enable || d.p.lock_readers) return GX_EINVAL;
-  uint32_t unlocked = 0;
-  int rc = gx_lock_census(e, &unlocked);
-  if (rc) return rc;
-  if (unlocked) return GX_EINVAL;  // a host here is free: the pairs must run the exchange
-  set_round_fields(e);
-  if (d.p.push_pull_mode == GX_PP_INITIATE) {  // once per exchange, by its initiator's shard (pp_schedule)
-    const uint32_t nb = pp_schedule(e);
-    const size_t n = e->pp_idx.size();
-    uint32_t n_first = 0, any = 0;
-    for (size_t t = 0; t < n; t++) {
-      const bool la = own(e, e->pp_host[t]), lb = own(e, e->pp_host[n + t]);
-      n_first += la ? 1u : 0u;
-      any |= (la || lb) ? 1u : 0u;
-    }
-    e->pp_cursor = nb;  // no batch is left to run
-    if (!n) return GX_OK;
-    k_ae_locked_note<<<1, 64, 0, e->stream>>>(d, n_first, any);
-    return phase_done(e);
-  }
-  uint32_t base[2] = {0, d.H / 2}, len[2] = {d.H, 0};
-  int ng = 1;
-  if (d.pair_split) {
-    len[0] = d.H / 2;
-    len[1] = d.H - d.H / 2;
-    ng = 2;
-  }
-  const uint32_t n0 = len[0] / 2, n1 = ng > 1 ? len[1] / 2 : 0, np = n0 + n1;
-  if (!np) return GX_OK;
-  const uint64_t key0 = rng4(d.p.seed, ST_AE, (uint64_t)d.round, base[0], 0);
-  const uint64_t key1 = ng > 1 ? rng4(d.p.seed, ST_AE, (uint64_t)d.round, base[1], 0) : 0;
-  std::vector<uint32_t> pa(np), pb(np);
-  k_ae_pairs<<<(np + 255) / 256, 256, 0, e->stream>>>(base[0], len[0], key0, base[1], ng > 1 ? len[1] : 0, key1, n0,
-                                                       np, e->ae_pa, e->ae_pb);
-  HIPCHK(hipMemcpyAsync(pa.data(), e->ae_pa, 4ull * np, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipMemcpyAsync(pb.data(), e->ae_pb, 4ull * np, hipMemcpyDeviceToHost, e->stream));
-  rc = sync_check(e);
-  if (rc) return rc;
-  uint32_t n_first = 0, any = 0;
-  for (uint32_t t = 0; t < np; t++) {
-    const bool la = own(e, pa[t]), lb = own(e, pb[t]);
-    n_first += la ? 1u : 0u;
-    any |= (la || lb) ? 1u : 0u;
-  }
-  k_ae_locked_note<<<1, 64, 0, e->stream>>>(d, n_first, any);
-  return phase_done(e);
 }
 
 int gx_round_end(gx_engine *e) {
@@ -3125,16 +2645,6 @@ int gx_probe_cross(gx_engine *e, uint64_t *out) {
   return GX_OK;
 }
 
-// Outside gx.h's declarations (described there with the sharded rounds): how many runs of the
-// push-pull chain gx_ae_bytes .. gx_ae_merge this round takes on a sharded engine: 0 when it is not
-// a push-pull round or nobody initiates, 1 for the matching, the batch count in GX_PP_INITIATE.
-// From (seed, round) on the host: no device work, the same answer on every shard.
-int gx_ae_batches(gx_engine *e, uint32_t *n) {
-  if (!e || !n) return GX_EINVAL;
-  *n = !ae_round(e) ? 0 : e->d.p.push_pull_mode == GX_PP_INITIATE ? pp_schedule(e) : 1;
-  return GX_OK;
-}
-
 // Diagnostics outside gx.h (env GX_KPROF at gx_create): the wall-clock phase marks (100 MHz) of the
 // last k_send launch, 8 per wave: start, ticks done, block barrier, sends begin, send_host begin,
 // first chunk planned, first chunk's records stored, sends done (0 = not reached).
@@ -3165,6 +2675,9 @@ int gx_converged(gx_engine *e, int *converged, uint64_t *n_disagree) {
 }
 
 }  // extern "C"
+
+// a sharded engine's push-pull chain: gx_ae_bytes .. gx_ae_merge, gx_ae_claim_*, gx_ae_skip_locked
+#include "gx_ae_chain_host.hpp"
 
 // full-state JSON codec: gx_set_names, gx_local_state_json, gx_decode_state_json,
 // gx_merge_remote_state_json
