@@ -84,7 +84,6 @@ static int ae_pairs_host(gx_engine *e, const AeMatching &m, std::vector<uint32_t
 static int ae_plan(gx_engine *e, uint64_t *bytes) {
   Dev &d = e->d;
   gx_engine::AeChain &c = e->chain;
-  set_round_fields(e);
   std::vector<uint32_t> pa, pb, pt;  // pt: each pair's index in the round's list (the messages' pair index)
   if (d.p.push_pull_mode == GX_PP_INITIATE) {
     // the batch at the cursor (ae_step_due): its exchanges, named by their place in initiator order
@@ -203,7 +202,6 @@ static void ae_plan_launch(gx_engine *e, uint32_t lo, uint32_t hi, const void *l
                            hipStream_t st = nullptr) {
   if (hi <= lo) return;
   if (!st) st = e->stream;
-  set_round_fields(e);
   LaunchTimer t(e, GX_K_AE, st);
   const AeIn in = ae_in(e, lead, ret);
   // fewer than 4 pairs per CU: per-block bandwidth decides (2 tiles in flight measured slower for
@@ -215,7 +213,6 @@ static void ae_plan_launch(gx_engine *e, uint32_t lo, uint32_t hi, const void *l
 // gx.h lock_readers: the pool rows of the cross pairs' admitted read-locked sides (k_ae_xdefer)
 static void ae_xdefer_launch(gx_engine *e, const void *lead) {
   if (!e->chain.n_pack) return;
-  set_round_fields(e);
   LaunchTimer t(e, GX_K_AE);
   const AeIn in = ae_in(e, lead, nullptr);
   with_flag(vec_of(e), [&](auto V) {
@@ -243,7 +240,7 @@ extern "C" {
 
 int gx_ae_bytes(gx_engine *e, uint64_t *bytes) {
   if (!e || !bytes) return GX_EINVAL;
-  HIPCHK(hipSetDevice(e->device));
+  GXTRY(enter(e, ENTRY_PHASE));
   gx_engine::AeChain &c = e->chain;
   for (uint32_t g = 0; g < e->d.G; g++) bytes[g] = 0;
   c.n_plan = c.n_pack = 0;
@@ -257,7 +254,7 @@ int gx_ae_pack(gx_engine *e, void *buf, uint64_t cap) {
   const uint32_t np = e->chain.n_pack;
   if (!np) return GX_OK;
   if (!ae_done(e, AE_PLANNED) || cap < np * dig_bytes(e)) return GX_EINVAL;
-  HIPCHK(hipSetDevice(e->device));
+  GXTRY(enter(e, ENTRY_PHASE));
   with_flags(vec_of(e), e->d.p.lock_readers != 0, [&](auto V, auto RO) {
     k_ae_digest<V(), RO()><<<np, 256, 0, e->stream>>>(e->d, e->ae_pack_host, e->ae_pack_t, e->ae_pack_other,
                                                       e->ae_pack_first, (uint8_t *)buf, e->ae_dig, e->nblk, e->ae_bcnt);
@@ -269,7 +266,7 @@ int gx_ae_pack(gx_engine *e, void *buf, uint64_t cap) {
 // offsets of this side's lead messages and of the partner's in the lead inbox.
 int gx_ae_delta_bytes(gx_engine *e, const void *digests, uint64_t bytes, uint64_t *out) {
   if (!e || !out || (bytes && !digests)) return GX_EINVAL;
-  HIPCHK(hipSetDevice(e->device));
+  GXTRY(enter(e, ENTRY_PHASE));
   Dev &d = e->d;
   gx_engine::AeChain &c = e->chain;
   for (uint32_t g = 0; g < d.G; g++) out[g] = 0;
@@ -303,7 +300,7 @@ int gx_ae_delta_pack(gx_engine *e, void *buf, uint64_t cap) {
   if (!e || (cap && !buf)) return GX_EINVAL;
   if (!e->chain.n_pack) return GX_OK;
   if (!ae_done(e, AE_DELTA) || cap < e->chain.lead_total) return GX_EINVAL;
-  HIPCHK(hipSetDevice(e->device));
+  GXTRY(enter(e, ENTRY_PHASE));
   launch_ae_lead_pack(e, buf);
   return phase_done(e);
 }
@@ -312,7 +309,7 @@ int gx_ae_delta_pack(gx_engine *e, void *buf, uint64_t cap) {
 // messages (gx.h "return").
 int gx_ae_return_bytes(gx_engine *e, const void *lead, uint64_t lead_bytes, uint64_t *out) {
   if (!e || !out || (lead_bytes && !lead)) return GX_EINVAL;
-  HIPCHK(hipSetDevice(e->device));
+  GXTRY(enter(e, ENTRY_PHASE));
   gx_engine::AeChain &c = e->chain;
   for (uint32_t g = 0; g < e->d.G; g++) out[g] = 0;
   c.done &= ~AE_RET;
@@ -337,14 +334,14 @@ int gx_ae_return_pack(gx_engine *e, const void *lead, uint64_t lead_bytes, void 
   const gx_engine::AeChain &c = e->chain;
   if (!c.n_pack) return GX_OK;
   if (!ae_done(e, AE_RET) || cap < c.ret_total || lead_bytes != c.lead_in_total) return GX_EINVAL;
-  HIPCHK(hipSetDevice(e->device));
+  GXTRY(enter(e, ENTRY_PHASE));
   launch_ae_ret<false>(e, lead, buf);
   return phase_done(e);
 }
 
 int gx_ae_merge_local(gx_engine *e) {
   if (!e) return GX_EINVAL;
-  HIPCHK(hipSetDevice(e->device));
+  GXTRY(enter(e, ENTRY_PHASE));
   if (!ae_step_due(e) || ae_done(e, AE_LOCAL)) return GX_OK;
   if (!ae_done(e, AE_PLANNED)) return GX_EINVAL;
   // on the side stream, after the rows are packed: the exchange layer's collectives (ordered
@@ -361,8 +358,7 @@ int gx_ae_merge_local(gx_engine *e) {
 
 int gx_ae_merge(gx_engine *e, const void *lead, uint64_t lead_bytes, const void *ret, uint64_t ret_bytes) {
   if (!e || (lead_bytes && !lead) || (ret_bytes && !ret)) return GX_EINVAL;
-  HIPCHK(hipSetDevice(e->device));
-  quiet_invalidate(e);
+  GXTRY(enter(e, ENTRY_PHASE));
   if (!ae_round(e)) return GX_OK;
   if (e->d.G < 2) {
     int rc = ae_whole_impl(e, false);
@@ -420,7 +416,7 @@ int gx_ae_merge(gx_engine *e, const void *lead, uint64_t lead_bytes, const void 
 // planned on this shard still answers (held slots, no claimants) and sets nothing.
 int gx_ae_claim_want(gx_engine *e, int64_t *want) {
   if (!e || !want || !ae_claims_on(e)) return GX_EINVAL;
-  HIPCHK(hipSetDevice(e->device));
+  GXTRY(enter(e, ENTRY_PHASE));
   const gx_engine::AeChain &c = e->chain;
   const bool due = ae_step_due(e);
   if (due && !ae_done(e, c.n_pack ? AE_PLANNED | AE_DELTA : AE_PLANNED)) return GX_EINVAL;
@@ -430,7 +426,6 @@ int gx_ae_claim_want(gx_engine *e, int64_t *want) {
   }
   int jr = join_side(e);  // ro_flag is written
   if (jr) return jr;
-  set_round_fields(e);
   const uint32_t np = due ? c.n_pack : 0, nl = due ? c.n_plan - np : 0;  // cross pairs, then local ones
   k_ae_want<<<1, 256, 0, e->stream>>>(e->d, e->ae_pa + np, e->ae_pb + np, nl, e->ae_pack_host, e->ae_rov, np,
                                       (long long *)want);
@@ -438,10 +433,9 @@ int gx_ae_claim_want(gx_engine *e, int64_t *want) {
 }
 int gx_ae_claim_set(gx_engine *e, const int64_t *won) {
   if (!e || !won || !ae_claims_on(e)) return GX_EINVAL;
-  HIPCHK(hipSetDevice(e->device));
+  GXTRY(enter(e, ENTRY_PHASE));
   if (!ae_step_due(e)) return GX_OK;
   if (!ae_done(e, AE_PLANNED | AE_LOCAL) || e->side_pending) return GX_EINVAL;
-  set_round_fields(e);
   const uint32_t lo = e->chain.n_pack, nl = e->chain.n_plan - lo;  // the local pairs
   {
     LaunchTimer t(e, GX_K_AE);
@@ -461,18 +455,16 @@ int gx_ae_claim_set(gx_engine *e, const int64_t *won) {
 // their merge to a host of another shard (the slot's holder, or a lower claimant). Waits for the device.
 int gx_ae_ro_counts(gx_engine *e, uint64_t *out) {
   if (!e || !out || !ae_claims_on(e)) return GX_EINVAL;
-  HIPCHK(hipSetDevice(e->device));
+  GXTRY(enter(e, ENTRY_READ));
   HIPCHK(hipMemcpyAsync(out, e->ro_xc, sizeof(uint64_t) * 3, hipMemcpyDeviceToHost, e->stream));
   return sync_check(e);
 }
 
 int gx_lock_census(gx_engine *e, uint32_t *unlocked) {
   if (!e || !unlocked) return GX_EINVAL;
-  HIPCHK(hipSetDevice(e->device));
-  int rc = ensure_api(e, sizeof(uint32_t));
-  if (rc) return rc;
-  set_round_fields(e);
-  uint32_t *dv = (uint32_t *)e->api.p;
+  GXTRY(enter(e, ENTRY_READ));
+  uint32_t *dv;
+  GXTRY(api_carve(e, region(dv, 1)));
   HIPCHK(hipMemsetAsync(dv, 0, sizeof(uint32_t), e->stream));
   if (e->d.Hl) k_lock_census<<<nblk(e->d.Hl, 256), 256, 0, e->stream>>>(e->d, dv);
   return read_back(e, dv, unlocked);
@@ -492,7 +484,7 @@ int gx_ae_skip_locked(gx_engine *e) {
   int rc = gx_lock_census(e, &unlocked);
   if (rc) return rc;
   if (unlocked) return GX_EINVAL;  // a host here is free: the pairs must run the exchange
-  set_round_fields(e);
+  GXTRY(enter(e, ENTRY_PHASE));
   if (d.p.push_pull_mode == GX_PP_INITIATE) {  // once per exchange, by its initiator's shard (pp_schedule)
     e->pp_cursor = pp_schedule(e);  // no batch is left to run
     const size_t n = e->pp_idx.size();

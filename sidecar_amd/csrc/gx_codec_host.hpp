@@ -425,7 +425,7 @@ int gx_set_names(gx_engine *e, const gx_names *in) {
     while (iht[s]) s = (s + 1) & (isz - 1);
     iht[s] = r + 1;
   }
-  HIPCHK(hipSetDevice(e->device));
+  GXTRY(enter(e, ENTRY_MUTATE));  // (the static message bytes, as gx_set_static_bytes)
   HIPCHK(hipStreamSynchronize(e->stream));
   codec_free(e);
   e->codec = new CodecState();
@@ -478,7 +478,7 @@ int gx_set_names(gx_engine *e, const gx_names *in) {
 int gx_local_state_json(gx_engine *e, uint32_t view, char *out, uint64_t cap, uint64_t *n_out) {
   if (!e || !own(e, view) || (cap && !out)) return GX_EINVAL;
   if (!e->codec) return GX_ENOENT;
-  HIPCHK(hipSetDevice(e->device));
+  GXTRY(enter(e, ENTRY_READ));
   return enc_impl(e, view, out, cap, n_out);
 }
 
@@ -486,7 +486,7 @@ int gx_decode_state_json(gx_engine *e, const char *buf, uint64_t len, gx_service
                          uint32_t *n_out, gx_decode_stats *ds) {
   if (!e || (len && !buf) || (cap && !out)) return GX_EINVAL;
   if (!e->codec) return GX_ENOENT;
-  HIPCHK(hipSetDevice(e->device));
+  GXTRY(enter(e, ENTRY_READ));
   gxc::Dec x;
   uint32_t n = 0;
   int rc = dec_impl(e, buf, len, ds, x, n);
@@ -506,8 +506,7 @@ int gx_decode_state_json(gx_engine *e, const char *buf, uint64_t len, gx_service
 int gx_merge_remote_state_json(gx_engine *e, uint32_t view, const char *buf, uint64_t len, gx_decode_stats *ds) {
   if (!e || !own(e, view) || (len && !buf)) return GX_EINVAL;
   if (!e->codec) return GX_ENOENT;
-  HIPCHK(hipSetDevice(e->device));
-  quiet_invalidate(e);
+  GXTRY(enter(e, ENTRY_MUTATE));
   gxc::Dec x;
   uint32_t n = 0;
   int rc = dec_impl(e, buf, len, ds, x, n);
@@ -518,7 +517,6 @@ int gx_merge_remote_state_json(gx_engine *e, uint32_t view, const char *buf, uin
   rc = dbuf(e->codec->out, sizeof(uint64_t) * d.R, &rowp);
   if (rc) return rc;
   uint64_t *row = (uint64_t *)rowp;
-  set_round_fields(e);
   const bool ev = !e->log_views.empty();
   {
     LaunchTimer t(e, GX_K_AE);
