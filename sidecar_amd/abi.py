@@ -249,6 +249,8 @@ ABI_FUNCS = [
     "gx_each_service_sorted", "gx_set_service_names", "gx_by_service",
 ]
 ALL_OWNERS = 0xFFFFFFFF
+WATCH_MAX, WATCH_OFF = 1024, 0xFFFFFFFF  # include/gx_watch.h
+WATCH_ANY = -(1 << 63)  # min_updated_ns INT64_MIN: every present slot holds the version
 
 
 def _declare(lib):
@@ -332,6 +334,17 @@ def _declare(lib):
         f = getattr(lib, name)
         f.argtypes = args
         f.restype = res
+    # include/gx_watch.h: symbols of the HIP engine, declared where the library has them
+    watch = {
+        "gx_watch_arm": ([vp, u32, u32], i32),
+        "gx_watch_set": ([vp, u32, P(u32), P(i64), u32], i32),
+        "gx_watch_read": ([vp, u32, u32, vp, vp, P(i64)], i32),
+    }
+    for name, (args, res) in watch.items():
+        if hasattr(lib, name):
+            f = getattr(lib, name)
+            f.argtypes = args
+            f.restype = res
     return lib
 
 
@@ -909,6 +922,41 @@ class Engine:
     def owner_words(self, ptr: int):
         """R words at ptr (device memory for the HIP engine): each record's word in its owner's view."""
         check(self.lib.gx_owner_words(self.h, C.c_void_p(ptr)), "gx_owner_words")
+
+    # record watch (include/gx_watch.h; HIP engine) -------------------------------------------
+    def watch_arm(self, n: int, log_rounds: int = 0):
+        """A watch of n entries (all off) with a zeroed log of log_rounds rounds, starting with the
+        round that ends next; n = 0 disarms and frees."""
+        check(self.lib.gx_watch_arm(self.h, int(n), int(log_rounds)), "gx_watch_arm")
+        self._watch_n = int(n)
+
+    def watch_set(self, first: int, keys, min_updated_ns):
+        """Rewrite entries [first, first + len(keys)): record keys (WATCH_OFF: entry off) and absolute
+        version thresholds (WATCH_ANY: any version). Counts from the next round end on."""
+        k = np.ascontiguousarray(np.asarray(keys, dtype=np.uint32).reshape(-1))
+        t = np.ascontiguousarray(np.asarray(min_updated_ns, dtype=np.int64).reshape(-1))
+        assert k.size == t.size
+        check(self.lib.gx_watch_set(self.h, int(first), k.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                    t.ctypes.data_as(C.POINTER(C.c_int64)), k.size), "gx_watch_set")
+
+    def watch_info(self):
+        """(first_round, n_logged, missed) of the armed watch (waits for the device)."""
+        info = (C.c_int64 * 3)()
+        check(self.lib.gx_watch_read(self.h, 0, 0, None, None, info), "gx_watch_read")
+        return int(info[0]), int(info[1]), int(info[2])
+
+    def watch_read(self, row: int = 0, rows: Optional[int] = None):
+        """Log rows [row, row + rows) (default: every logged row from `row` on), waiting for the
+        device: (counts uint32 [rows, n, 2] = holds, older; live uint32 [rows]; first_round; n_logged;
+        missed). Row k is round first_round + k."""
+        first_round, n_logged, missed = self.watch_info()
+        rows = n_logged - row if rows is None else rows
+        counts = np.zeros((max(0, rows), self._watch_n, 2), dtype=np.uint32)
+        live = np.zeros(max(0, rows), dtype=np.uint32)
+        info = (C.c_int64 * 3)()
+        check(self.lib.gx_watch_read(self.h, int(row), int(rows), counts.ctypes.data_as(C.c_void_p),
+                                     live.ctypes.data_as(C.c_void_p), info), "gx_watch_read")
+        return counts, live, first_round, n_logged, missed
 
     # memberlist failure detection (SURVEY §8f-3) ---------------------------------------------
     def fd_members(self, host: int, lo: int = 0, hi: Optional[int] = None) -> bytes:

@@ -20,6 +20,8 @@
 //                    broadcast FIFO with a wave ballot
 //   5   k_ae         anti-entropy push-pull: one 256-thread block per host pair streams both views
 //                    and merges each into the other (services_delegate.go:153-167, Merge :367-373)
+//   end k_watch      only while a record watch is armed (gx_watch.h): per watched record, the views
+//                    that hold its version and those that hold an older one, into the round's log row
 // No MFMA: the work is int64 compare/select over HBM-resident views (memory-bound).
 #include <hip/hip_runtime.h>
 
@@ -59,6 +61,7 @@ static uint32_t pow2_at_least(uint32_t x) {
   return v;
 }
 
+#include "../../include/gx_watch.h"
 #include "gx_kernels.hpp"
 #include "gx_fd.hpp"
 #include "gx_codec.hpp"
@@ -268,6 +271,17 @@ struct gx_engine {
   uint32_t scan_nch;
   grec *scan_tmp;
   ScanChunk *scan_chunk;
+  // the record watch (gx_watch.h, gx_watch_host.hpp): armed while n != 0; its buffers are in `mem`
+  struct Watch {
+    uint32_t n, log_rounds;
+    int64_t first_round;  // the round of log row 0
+    uint64_t missed;      // rounds that ended past the log's last row
+    uint32_t *keys;       // [n] record keys, GX_WATCH_OFF = entry off
+    uint64_t *thr;        // [n] thresholds as packed words of status 0 (k_watch)
+    uint32_t *log;        // [log_rounds][n + 1] {holds, older} per entry, then {live, 0}
+    std::vector<uint32_t> keys_host;  // the entries as last set: gx_watch_set stages its copies from here
+    std::vector<uint64_t> thr_host;
+  } watch;
 };
 
 static void codec_free(gx_engine *e);  // gx_codec_host.hpp
@@ -571,7 +585,8 @@ static void quiet_invalidate(gx_engine *e) {
 enum Entry {
   ENTRY_READ,    // leaves everything a round reads as it is (copies out, computes into scratch, sets
                  // ByService's name ranks): the quiet-round bounds stand
-  ENTRY_MUTATE,  // changes catalog, queue, memberlist, listener or stream state between rounds
+  ENTRY_MUTATE,  // changes catalog, queue, memberlist, listener or stream state between rounds, or
+                 // the record watch's entries (gx_watch_arm, gx_watch_set)
   ENTRY_PHASE,   // one piece of a round the caller drives itself (gx_round_*, gx_outbox_*, gx_ae_*)
   ENTRY_ROUNDS,  // gx_run_rounds alone: the one entry that runs rounds and keeps the bounds, which
                  // describe exactly the rounds it runs
@@ -967,6 +982,29 @@ static int ae_whole_impl(gx_engine *e, bool quiet) {
   return GX_OK;
 }
 
+// The one place a round ends (run_one_round, gx_round_end): every phase of round d.round is queued
+// on the engine's stream. With a watch armed (gx_watch.h) the round's counts are taken here, from
+// the views as those phases leave them, into the round's row of the log; past the last row the round
+// is only counted. Without one nothing is launched. Then the round number moves.
+#define WATCH_GRID 512  // blocks per entry group: 64 views each at cfg 5, 128 atomics per block
+static int watch_round_end(gx_engine *e) {
+  gx_engine::Watch &w = e->watch;
+  Dev &d = e->d;
+  if (w.n) {
+    const int64_t k = d.round - w.first_round;
+    if (k >= (int64_t)w.log_rounds) {
+      w.missed++;
+    } else if (d.Hl) {
+      LaunchTimer t(e, GX_K_CONVERGE);
+      const unsigned gx = std::min(nblk(d.Hl, WATCH_VIEWS), (unsigned)WATCH_GRID);
+      k_watch<<<dim3(gx, nblk(w.n, 64)), 256, 0, e->stream>>>(d, w.keys, w.thr, w.n, w.log + 2 * ((size_t)w.n + 1) * (size_t)k);
+      HIPCHK(hipGetLastError());
+    }
+  }
+  d.round++;
+  return GX_OK;
+}
+
 // A quiet round (quiet_round, decided in round_send_impl) has no receive phase: no inbox was written
 // and every pipeline is full and stays (k_lock_append and k_merge_seg would find nothing).
 static int run_one_round(gx_engine *e) {
@@ -975,7 +1013,7 @@ static int run_one_round(gx_engine *e) {
   e->quiet_now = false;
   if (!rc && !quiet) rc = round_merge_impl(e);
   if (!rc) rc = ae_whole_impl(e, quiet);
-  if (!rc) e->d.round++;
+  if (!rc) rc = watch_round_end(e);
   return rc;
 }
 
@@ -1623,7 +1661,7 @@ int gx_round_end(gx_engine *e) {
   GXTRY(enter(e, ENTRY_PHASE));
   int rc = join_side(e);
   if (rc) return rc;
-  e->d.round++;
+  GXTRY(watch_round_end(e));
   e->pp_cursor = 0;
   rc = wake_all(e);
   return rc ? rc : phase_done(e);
@@ -1677,6 +1715,9 @@ int gx_round_gossip_end(gx_engine *e, const void *buf, uint64_t bytes, int *ae) 
 
 // the single-host calls: catalog, readers, listeners, memberlist, stats and diagnostics
 #include "gx_api_host.hpp"
+
+// the record watch of include/gx_watch.h: gx_watch_arm, gx_watch_set, gx_watch_read
+#include "gx_watch_host.hpp"
 
 // a sharded engine's push-pull chain: gx_ae_bytes .. gx_ae_merge, gx_ae_claim_*, gx_ae_skip_locked
 #include "gx_ae_chain_host.hpp"

@@ -5278,6 +5278,59 @@ __global__ void k_owner_words(Dev d, uint64_t *out) {
   out[r] = o - d.lo < d.Hl ? d.view[(size_t)(o - d.lo) * d.R + r] : 0ull;
 }
 
+// ======================================================================== record watch ==
+// gx_watch.h: one round's counts for the watched records, over this engine's views as the round's
+// last phase left them (launched by watch_round_end, before the round number moves). Lane = watch
+// entry (blockIdx.y: its group of 64), so a wave's load is 64 gathers from one view row, each its
+// own 128-B line unless entries share an owner; a block walks the contiguous views [v0, v1) of its
+// share, wave w the views v0 + w, v0 + w + 4, ..., WATCH_PF of them in flight per thread. Counts stay
+// in registers; the block's waves meet in LDS and add one pair per entry into the round's row (zero
+// since gx_watch_arm: each row is written by one launch). An entry's threshold is a packed word with
+// status 0, so `present and Updated >= T` is one unsigned compare. Departed views are left out by
+// k_view_minmax's rule; the entry groups' first column of blocks counts the others once (`live`).
+#define WATCH_PF 4
+#define WATCH_VIEWS (4 * WATCH_PF)  // the fewest views worth a block: one load per wave and flight slot
+__global__ void __launch_bounds__(256) k_watch(Dev d, const uint32_t *keys, const uint64_t *thr, uint32_t n, uint32_t *row) {
+  __shared__ uint32_t part[4][64][2];
+  __shared__ uint32_t live_part[4];
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const uint32_t i = blockIdx.y * 64u + lane;
+  const uint32_t key = i < n ? keys[i] : GX_WATCH_OFF;
+  const bool on = key != GX_WATCH_OFF;
+  const uint64_t t = on ? thr[i] : 0;
+  const uint32_t v0 = (uint32_t)(((uint64_t)blockIdx.x * d.Hl) / gridDim.x);
+  const uint32_t v1 = (uint32_t)(((uint64_t)(blockIdx.x + 1) * d.Hl) / gridDim.x);
+  const uint64_t *col = d.view + (on ? key : 0u);
+  uint32_t holds = 0, older = 0, live = 0;
+  for (uint32_t v = v0 + wave; v < v1; v += 4 * WATCH_PF) {
+    uint64_t w[WATCH_PF];
+#pragma unroll
+    for (int u = 0; u < WATCH_PF; u++) {
+      const uint32_t vv = v + 4u * u;  // wave-uniform, like `in`
+      const bool in = vv < v1 && !departed(d, d.lo + vv);
+      live += in ? 1u : 0u;
+      w[u] = in && on ? col[(size_t)vv * d.R] : GX_SLOT_ABSENT;
+    }
+#pragma unroll
+    for (int u = 0; u < WATCH_PF; u++) {
+      const bool present = st_of(w[u]) != GX_ABSENT;
+      holds += present && w[u] >= t ? 1u : 0u;
+      older += present && w[u] < t ? 1u : 0u;
+    }
+  }
+  part[wave][lane][0] = holds;
+  part[wave][lane][1] = older;
+  if (lane == 0) live_part[wave] = live;
+  __syncthreads();
+  if (wave) return;
+  holds = part[0][lane][0] + part[1][lane][0] + part[2][lane][0] + part[3][lane][0];
+  older = part[0][lane][1] + part[1][lane][1] + part[2][lane][1] + part[3][lane][1];
+  if (holds) atomicAdd(&row[2 * i], holds);  // (an entry past n or off counted nothing)
+  if (older) atomicAdd(&row[2 * i + 1], older);
+  live = live_part[0] + live_part[1] + live_part[2] + live_part[3];
+  if (blockIdx.y == 0 && lane == 0 && live) atomicAdd(&row[2 * n], live);
+}
+
 // ================================================================ convergence / digests ==
 __global__ void k_converged(Dev d, unsigned long long *bad) {
   uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;

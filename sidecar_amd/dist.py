@@ -272,6 +272,25 @@ class ShardRounds:
                 for s in self.shards:
                     s.e.round_end()
 
+    def watch_arm(self, n: int, log_rounds: int = 0):
+        """A record watch on every held shard (include/gx_watch.h): each counts its own views."""
+        for e in self.engines:
+            e.watch_arm(n, log_rounds)
+
+    def watch_set(self, first: int, keys, min_updated_ns):
+        for e in self.engines:
+            e.watch_set(first, keys, min_updated_ns)
+
+    def watch_read(self, row: int = 0, rows=None):
+        """The cluster's log: the shards' logs summed over all G shards (one reduction, made here and
+        in no round). Returns what Engine.watch_read returns; the shards end the same rounds, so
+        first_round, n_logged and missed are any shard's."""
+        got = [e.watch_read(row, rows) for e in self.engines]
+        counts, live, first_round, n_logged, missed = got[0]
+        t = torch.tensor(np.stack([np.concatenate([c.reshape(-1), l]).astype(np.int64) for c, l, *_ in got]))
+        s = self._reduce(t, "sum").cpu().numpy().astype(np.uint32)
+        return s[:counts.size].reshape(counts.shape), s[counts.size:], first_round, n_logged, missed
+
     def stats(self) -> dict:
         """The cluster's counters: summed over the shards, but the latest `round` and
         `last_change_round` and the earliest of each FIRST_ROUND_STATS (-1: in no shard)."""
