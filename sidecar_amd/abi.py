@@ -249,6 +249,30 @@ ABI_FUNCS = [
     "gx_each_service_sorted", "gx_set_service_names", "gx_by_service",
 ]
 ALL_OWNERS = 0xFFFFFFFF
+CKPT_MAX_SECTIONS = 64  # include/gx_ckpt.h
+CKPT_RAW, CKPT_VIEWS = 0, 1
+CK_VIEW, CK_SRVT = 1, 27  # section ids (GX_CK_*) the tools name
+# the params a fork may change (gx_ckpt.h FORK)
+CKPT_FORK_FIELDS = ("device", "partition_start", "partition_end", "storm_round", "depart_round", "depart_ppm")
+
+
+class GxCkptSection(C.Structure):
+    _fields_ = [("id", C.c_uint32), ("coding", C.c_uint32), ("raw_bytes", C.c_uint64), ("stored_bytes", C.c_uint64)]
+
+
+class GxCkptInfo(C.Structure):
+    _fields_ = [("n_sections", C.c_uint32), ("pad", C.c_uint32), ("raw_bytes", C.c_uint64),
+                ("stored_bytes", C.c_uint64), ("file_bytes", C.c_uint64), ("coder_ms", C.c_float),
+                ("base_ms", C.c_float), ("count_ms", C.c_float), ("emit_ms", C.c_float),
+                ("views_raw", C.c_uint32), ("chunks", C.c_uint32), ("sections", GxCkptSection * CKPT_MAX_SECTIONS)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k not in ("pad", "sections")}
+        d["sections"] = {s.id: {"coding": s.coding, "raw_bytes": s.raw_bytes, "stored_bytes": s.stored_bytes}
+                         for s in self.sections[:min(self.n_sections, CKPT_MAX_SECTIONS)]}
+        return d
+
+
 WATCH_MAX, WATCH_OFF = 1024, 0xFFFFFFFF  # include/gx_watch.h
 WATCH_ANY = -(1 << 63)  # min_updated_ns INT64_MIN: every present slot holds the version
 
@@ -334,13 +358,18 @@ def _declare(lib):
         f = getattr(lib, name)
         f.argtypes = args
         f.restype = res
-    # include/gx_watch.h: symbols of the HIP engine, declared where the library has them
-    watch = {
+    # symbols of the HIP engine alone, declared where the library has them
+    hip_only = {
+        # include/gx_watch.h
         "gx_watch_arm": ([vp, u32, u32], i32),
         "gx_watch_set": ([vp, u32, P(u32), P(i64), u32], i32),
         "gx_watch_read": ([vp, u32, u32, vp, vp, P(i64)], i32),
+        # include/gx_ckpt.h
+        "gx_ckpt_save": ([vp, C.c_char_p, P(GxCkptInfo)], i32),
+        "gx_ckpt_params": ([C.c_char_p, P(GxParams), P(i64)], i32),
+        "gx_ckpt_load": ([C.c_char_p, P(GxParams), P(vp), P(GxCkptInfo)], i32),
     }
-    for name, (args, res) in watch.items():
+    for name, (args, res) in hip_only.items():
         if hasattr(lib, name):
             f = getattr(lib, name)
             f.argtypes = args
@@ -370,12 +399,28 @@ def load_product():
 
 
 class GxError(RuntimeError):
-    pass
+    rc = None  # the C-ABI call's result where check() raised it
 
 
 def check(rc: int, what: str = ""):
     if rc != GX_OK:
-        raise GxError(f"{what} failed with rc={rc}")
+        err = GxError(f"{what} failed with rc={rc}")
+        err.rc = rc
+        raise err
+
+
+def _ckpt_fn(lib, name):
+    """A symbol of include/gx_ckpt.h; the CPU oracle has none: GX_ENOSYS."""
+    if not hasattr(lib, name):
+        check(GX_ENOSYS, name)
+    return getattr(lib, name)
+
+
+def ckpt_params(lib, path):
+    """(GxParams, round) of a checkpoint file's header (gx_ckpt_params: no device is touched)."""
+    p, r = GxParams(), C.c_int64()
+    check(_ckpt_fn(lib, "gx_ckpt_params")(os.fsencode(path), C.byref(p), C.byref(r)), "gx_ckpt_params")
+    return p, r.value
 
 
 def default_params(lib=None, **kw) -> GxParams:
@@ -417,6 +462,12 @@ class Engine:
         else:
             for k, v in kw.items():
                 setattr(params, k, v)
+        self._set_params(params)
+        h = C.c_void_p()
+        check(self.lib.gx_create(C.byref(params), C.byref(h)), "gx_create")
+        self.h = h
+
+    def _set_params(self, params: GxParams):
         self.params = params
         self.H = params.n_hosts
         self.S = params.n_services
@@ -424,9 +475,36 @@ class Engine:
         gid = params.shard_id if self.G > 1 else 0
         self.lo = (gid * self.H) // self.G
         self.hi = ((gid + 1) * self.H) // self.G
-        h = C.c_void_p()
-        check(self.lib.gx_create(C.byref(params), C.byref(h)), "gx_create")
+
+    # checkpoints (include/gx_ckpt.h; HIP engine) ---------------------------------------------
+    def ckpt_save(self, path) -> dict:
+        """The engine's state between two rounds, to `path`. Returns gx_ckpt_info as a dict: totals,
+        the view coder's device times, and per section id the raw and stored bytes."""
+        info = GxCkptInfo()
+        check(_ckpt_fn(self.lib, "gx_ckpt_save")(self.h, os.fsencode(path), C.byref(info)), "gx_ckpt_save")
+        return info.as_dict()
+
+    @classmethod
+    def from_checkpoint(cls, path, lib=None, **override) -> "Engine":
+        """An engine restored from a checkpoint file. override: the params a fork may change
+        (CKPT_FORK_FIELDS, each event only while it has not begun at the saved round; anything else
+        is GX_EINVAL). The stream mode, listeners, the record watch and the codec's name tables are
+        not part of a checkpoint. `ckpt_info` holds the load's gx_ckpt_info."""
+        lib = lib if lib is not None else load_product()
+        load = _ckpt_fn(lib, "gx_ckpt_load")
+        p, _ = ckpt_params(lib, path)
+        for k, v in override.items():
+            if not hasattr(p, k):
+                raise KeyError(k)
+            setattr(p, k, v)
+        h, info = C.c_void_p(), GxCkptInfo()
+        check(load(os.fsencode(path), C.byref(p) if override else None, C.byref(h), C.byref(info)), "gx_ckpt_load")
+        self = cls.__new__(cls)
+        self.lib = lib
+        self._set_params(p)
         self.h = h
+        self.ckpt_info = info.as_dict()
+        return self
 
     # lifecycle -------------------------------------------------------------------------
     def close(self):

@@ -62,6 +62,7 @@ static uint32_t pow2_at_least(uint32_t x) {
 }
 
 #include "../../include/gx_watch.h"
+#include "../../include/gx_ckpt.h"
 #include "gx_kernels.hpp"
 #include "gx_fd.hpp"
 #include "gx_codec.hpp"
@@ -75,40 +76,60 @@ struct TimedLaunch {
 // Device allocations that share one lifetime (an engine's, the codec's name tables, one call's
 // temporaries): every take() is freed by release(), at the latest when the owner goes.
 struct DevMem {
-  std::vector<void *> ptrs;
+  // id: the buffer's checkpoint section (gx_ckpt.h GX_CK_*: class STATE, saved), 0 = class DERIVED
+  // (not saved: some kernel rewrites it before anything reads it) or not an engine buffer at all
+  struct Buf {
+    void *p;
+    size_t bytes;
+    uint32_t id;
+  };
+  std::vector<Buf> bufs;
   DevMem() = default;
   DevMem(const DevMem &) = delete;
   DevMem &operator=(const DevMem &) = delete;
   ~DevMem() { release(); }
   template <class T>
-  int take(T *&p, size_t bytes) {
+  int take(uint32_t id, T *&p, size_t bytes) {
     void *q = nullptr;
     if (hipMalloc(&q, bytes) != hipSuccess) {
       (void)hipGetLastError();
       return GX_ENOMEM;
     }
-    ptrs.push_back(q);
+    bufs.push_back({q, bytes, id});
     p = (T *)q;
     return GX_OK;
   }
   // ... with every byte set to `fill` on stream s, so before whatever s runs next (a hipMemset on the
   // null stream is ordered with neither the host nor a non-blocking stream)
   template <class T>
-  int take(T *&p, size_t bytes, int fill, hipStream_t s) {
-    GXTRY(take(p, bytes));
+  int take(uint32_t id, T *&p, size_t bytes, int fill, hipStream_t s) {
+    GXTRY(take(id, p, bytes));
     if (bytes) HIPCHK(hipMemsetAsync(p, fill, bytes, s));
     return GX_OK;
+  }
+  template <class T>
+  int take(T *&p, size_t bytes) {
+    return take(0u, p, bytes);
+  }
+  template <class T>
+  int take(T *&p, size_t bytes, int fill, hipStream_t s) {
+    return take(0u, p, bytes, fill, s);
   }
   // one buffer (or none: p == nullptr) ahead of the rest
   template <class T>
   void drop(T *&p) {
-    ptrs.erase(std::remove(ptrs.begin(), ptrs.end(), (void *)p), ptrs.end());
+    bufs.erase(std::remove_if(bufs.begin(), bufs.end(), [&](const Buf &b) { return b.p == (void *)p; }), bufs.end());
     (void)hipFree(p);
     p = nullptr;
   }
+  const Buf *find(uint32_t id) const {
+    for (const Buf &b : bufs)
+      if (b.id == id) return &b;
+    return nullptr;
+  }
   void release() {
-    for (void *q : ptrs) (void)hipFree(q);
-    ptrs.clear();
+    for (const Buf &b : bufs) (void)hipFree(b.p);
+    bufs.clear();
   }
 };
 
@@ -158,6 +179,9 @@ struct gx_engine {
   hipStream_t side_stream;
   hipEvent_t side_start, side_done;
   bool side_pending;
+  // a round is open: gx_round_send / gx_round_gossip_begin ran and gx_round_end has not (gx_ckpt.h:
+  // gx_ckpt_save is refused until it has)
+  bool round_open;
   // Where a round's expiry scans run (round_send_impl): in k_send's prologue (one launch with the
   // owner ticks and the sends; a block streams its own listed views, fine while almost no view
   // needs a scan) or, while views do get scanned, in k_owner + k_scan + k_send, where k_scan
@@ -1260,7 +1284,11 @@ static int create_streams(gx_engine *e) {
   return GX_OK;
 }
 
-// TAKE(ptr, bytes[, fill byte, s]): one engine buffer, filled on the engine's stream
+// TAKE(class, ptr, bytes[, fill byte, s]): one engine buffer, filled on the engine's stream. Its
+// class is STATE, named by its checkpoint section (gx_ckpt.h GX_CK_*: gx_ckpt_save writes it,
+// gx_ckpt_load restores it), or DERIVED with the reason nothing reads it before it is rewritten: after
+// a load it is as this function leaves it. In doubt a buffer is STATE.
+#define DERIVED 0u
 #define TAKE(...) GXTRY(e->mem.take(__VA_ARGS__))
 
 static int create_buffers(gx_engine *e) {
@@ -1270,111 +1298,112 @@ static int create_buffers(gx_engine *e) {
   // per-host arrays hold this shard's Hl hosts; the message table also takes the packets received
   // from other shards (at most (H - Hl) * K), so it is sized H * K.
   const size_t Hg = d.H, H = d.Hl, K = d.KE ? d.KE : 1;
-  TAKE(d.view, sizeof(uint64_t) * H * d.R);
-  TAKE(d.own_status, H * d.S);
-  TAKE(d.hs, sizeof(gx_host_state) * H);
-  TAKE(d.fifo, sizeof(gx_job) * H * d.Q);
-  TAKE(d.sleep, sizeof(gx_sleeper) * H * d.SQ);
-  TAKE(d.dq, sizeof(grec) * H * d.DQ);
-  TAKE(d.arena, sizeof(grec) * H * d.A * d.L);
-  TAKE(d.arena_len, sizeof(uint32_t) * H * d.A, 0, s);
-  TAKE(d.arena_bits, sizeof(uint32_t) * H * d.AW);
-  TAKE(d.msg, sizeof(grec) * Hg * K * p->packet_cap);
-  TAKE(d.msg_w0, sizeof(uint64_t) * Hg * K * p->packet_cap);
-  TAKE(d.msg_len, sizeof(uint32_t) * Hg * K, 0, s);
-  TAKE(d.msg_dst, sizeof(uint32_t) * Hg * K);
-  TAKE(d.msg_key, sizeof(uint32_t) * Hg * K);
-  TAKE(e->in_cnt_buf, sizeof(uint32_t) * 2 * H, 0, s);
-  TAKE(d.in_hdr, sizeof(uint4) * H * d.DI);
-  TAKE(d.in_ovf, sizeof(uint4) * Hg * K);
-  TAKE(d.in_rec, sizeof(grec) * H * d.DR * p->packet_cap);
-  TAKE(d.work_cnt, sizeof(uint32_t) * GX_WC_N, 0, s);
-  TAKE(d.quiet_w, sizeof(uint32_t) * 2 * d.QW, 0, s);  // (0: no round is quiet)
-  TAKE(d.work, sizeof(uint32_t) * H);
+  TAKE(GX_CK_VIEW, d.view, sizeof(uint64_t) * H * d.R);
+  TAKE(GX_CK_OWN_STATUS, d.own_status, H * d.S);
+  TAKE(GX_CK_HS, d.hs, sizeof(gx_host_state) * H);
+  TAKE(GX_CK_FIFO, d.fifo, sizeof(gx_job) * H * d.Q);
+  TAKE(GX_CK_SLEEP, d.sleep, sizeof(gx_sleeper) * H * d.SQ);
+  TAKE(GX_CK_DQ, d.dq, sizeof(grec) * H * d.DQ);
+  TAKE(GX_CK_ARENA, d.arena, sizeof(grec) * H * d.A * d.L);
+  TAKE(GX_CK_ARENA_LEN, d.arena_len, sizeof(uint32_t) * H * d.A, 0, s);
+  TAKE(GX_CK_ARENA_BITS, d.arena_bits, sizeof(uint32_t) * H * d.AW);
+  TAKE(GX_CK_MSG, d.msg, sizeof(grec) * Hg * K * p->packet_cap);
+  TAKE(GX_CK_MSG_W0, d.msg_w0, sizeof(uint64_t) * Hg * K * p->packet_cap);
+  TAKE(GX_CK_MSG_LEN, d.msg_len, sizeof(uint32_t) * Hg * K, 0, s);
+  TAKE(GX_CK_MSG_DST, d.msg_dst, sizeof(uint32_t) * Hg * K);
+  TAKE(GX_CK_MSG_KEY, d.msg_key, sizeof(uint32_t) * Hg * K);
+  TAKE(GX_CK_IN_CNT, e->in_cnt_buf, sizeof(uint32_t) * 2 * H, 0, s);
+  TAKE(GX_CK_IN_HDR, d.in_hdr, sizeof(uint4) * H * d.DI);
+  TAKE(GX_CK_IN_OVF, d.in_ovf, sizeof(uint4) * Hg * K);
+  TAKE(GX_CK_IN_REC, d.in_rec, sizeof(grec) * H * d.DR * p->packet_cap);
+  TAKE(GX_CK_WORK_CNT, d.work_cnt, sizeof(uint32_t) * GX_WC_N, 0, s);
+  TAKE(DERIVED, d.quiet_w, sizeof(uint32_t) * 2 * d.QW, 0, s);  // (0: no round is quiet); DERIVED: tagged by the host's bound sequence, which restarts: k_send rewrites its wave's word before the host trusts any bound (quiet_from)
+  TAKE(GX_CK_WORK, d.work, sizeof(uint32_t) * H);
   if (p->push_pull_mode == GX_PP_INITIATE && d.G < 2) {  // a sharded engine's batches go through ae_pa, ae_pb
-    TAKE(e->pp_dev, sizeof(uint32_t) * 2 * Hg);
-    TAKE(e->pp_prow, sizeof(int32_t) * Hg, 0xff, s);
+    TAKE(DERIVED, e->pp_dev, sizeof(uint32_t) * 2 * Hg);  // DERIVED: ae_initiate copies the round's schedule in before its launches
+    TAKE(DERIVED, e->pp_prow, sizeof(int32_t) * Hg, 0xff, s);  // DERIVED: constant: all -1 since gx_create
   }
-  TAKE(d.mrec, sizeof(uint32_t) * H, 0, s);
-  TAKE(d.minexp, sizeof(unsigned long long) * H);
-  TAKE(d.scan_list, sizeof(grec) * H * d.L);
-  TAKE(d.scan_cnt, sizeof(uint32_t) * H);
+  TAKE(GX_CK_MREC, d.mrec, sizeof(uint32_t) * H, 0, s);
+  TAKE(GX_CK_MINEXP, d.minexp, sizeof(unsigned long long) * H);
+  TAKE(GX_CK_SCAN_LIST, d.scan_list, sizeof(grec) * H * d.L);
+  TAKE(GX_CK_SCAN_CNT, d.scan_cnt, sizeof(uint32_t) * H);
   if (e->scan_nch > 1) {
-    TAKE(e->scan_tmp, sizeof(grec) * H * e->scan_nch * d.L);
-    TAKE(e->scan_chunk, sizeof(ScanChunk) * H * e->scan_nch);
+    TAKE(DERIVED, e->scan_tmp, sizeof(grec) * H * e->scan_nch * d.L);  // DERIVED: k_scan_split writes a row's chunks before k_scan_join reads them, in the same round
+    TAKE(DERIVED, e->scan_chunk, sizeof(ScanChunk) * H * e->scan_nch);  // DERIVED: as scan_tmp
   }
-  TAKE(d.tick, H, 0, s);
-  TAKE(d.sbytes, sizeof(uint16_t) * d.R);
-  TAKE(d.srvt, sizeof(gx_server_times) * H * Hg);
-  TAKE(d.vlc, sizeof(int64_t) * H);
-  TAKE(d.ev_slot, sizeof(int32_t) * H, 0xff, s);  // -1: no listener
-  TAKE(d.ctr, sizeof(DevCtr), 0, s);
+  TAKE(GX_CK_TICK, d.tick, H, 0, s);
+  TAKE(GX_CK_SBYTES, d.sbytes, sizeof(uint16_t) * d.R);
+  TAKE(GX_CK_SRVT, d.srvt, sizeof(gx_server_times) * H * Hg);
+  TAKE(GX_CK_VLC, d.vlc, sizeof(int64_t) * H);
+  TAKE(DERIVED, d.ev_slot, sizeof(int32_t) * H, 0xff, s);  // -1: no listener; DERIVED: listeners are not part of a checkpoint: -1 as created
+  TAKE(GX_CK_CTR, d.ctr, sizeof(DevCtr), 0, s);
   if (p->fd_enable) {  // member rows of this shard's hosts
-    TAKE(d.mem, sizeof(gx_member) * H * Hg);
-    TAKE(d.fd_dl, sizeof(int32_t) * H * Hg);
-    TAKE(d.fdh, sizeof(gx_fd_host) * H);
-    TAKE(d.fdm, sizeof(gx_fd_msg) * Hg * K * p->fd_msg_cap);
-    TAKE(d.fd_len, sizeof(uint32_t) * Hg * K, 0, s);
-    TAKE(d.fd_peers, sizeof(uint32_t) * H * K);
-    TAKE(d.fd_np, sizeof(uint32_t) * H);
-    if (p->fd_push_pull_state) TAKE(d.fd_snap, sizeof(uint64_t) * H * Hg);
+    TAKE(GX_CK_MEM, d.mem, sizeof(gx_member) * H * Hg);
+    TAKE(GX_CK_FD_DL, d.fd_dl, sizeof(int32_t) * H * Hg);
+    TAKE(GX_CK_FDH, d.fdh, sizeof(gx_fd_host) * H);
+    TAKE(GX_CK_FDM, d.fdm, sizeof(gx_fd_msg) * Hg * K * p->fd_msg_cap);
+    TAKE(GX_CK_FD_LEN, d.fd_len, sizeof(uint32_t) * Hg * K, 0, s);
+    TAKE(GX_CK_FD_PEERS, d.fd_peers, sizeof(uint32_t) * H * K);
+    TAKE(GX_CK_FD_NP, d.fd_np, sizeof(uint32_t) * H);
+    if (p->fd_push_pull_state) TAKE(GX_CK_FD_SNAP, d.fd_snap, sizeof(uint64_t) * H * Hg);
   }
   if (p->lock_model) {  // locked hosts' inbound pipelines and waiting ExpireServer calls (gx.h lock_model)
-    TAKE(d.lkb, sizeof(grec) * H * d.C);
-    if (p->storm_round >= 0 || p->fd_enable) TAKE(d.pexp, sizeof(uint32_t) * H * d.PW, 0, s);
+    TAKE(GX_CK_LKB, d.lkb, sizeof(grec) * H * d.C);
+    if (p->storm_round >= 0 || p->fd_enable) TAKE(GX_CK_PEXP, d.pexp, sizeof(uint32_t) * H * d.PW, 0, s);
     if (p->lock_readers) {  // the waiting push-pull merges' pool (gx.h lock_readers)
-      TAKE(d.dpool, sizeof(uint64_t) * d.P * d.R);
-      TAKE(d.dpool_host, sizeof(uint32_t) * d.P, 0xff, s);
-      TAKE(d.dpool_res, sizeof(uint32_t) * d.P, 0, s);
-      TAKE(d.ro_flag, H, 0, s);
-      TAKE(d.ro_list, sizeof(uint32_t) * H);
-      TAKE(d.ro_n, sizeof(uint32_t), 0, s);
-      TAKE(d.dslot, sizeof(uint32_t) * Hg, 0xff, s);  // each host's slot, the claimants' bits
-      TAKE(d.claim_bits, sizeof(uint32_t) * ((Hg + 31) / 32), 0, s);
+      TAKE(GX_CK_DPOOL, d.dpool, sizeof(uint64_t) * d.P * d.R);
+      TAKE(GX_CK_DPOOL_HOST, d.dpool_host, sizeof(uint32_t) * d.P, 0xff, s);
+      TAKE(GX_CK_DPOOL_RES, d.dpool_res, sizeof(uint32_t) * d.P, 0, s);
+      TAKE(DERIVED, d.ro_flag, H, 0, s);  // DERIVED: k_ae_claim clears every flag it lists: zero between rounds, as created
+      TAKE(DERIVED, d.ro_list, sizeof(uint32_t) * H);  // DERIVED: k_ae_claim writes the list before k_ae_rox reads it
+      TAKE(DERIVED, d.ro_n, sizeof(uint32_t), 0, s);  // DERIVED: k_ae_claim writes it before k_ae_rox reads it
+      TAKE(GX_CK_DSLOT, d.dslot, sizeof(uint32_t) * Hg, 0xff, s);  // each host's slot, the claimants' bits
+      TAKE(DERIVED, d.claim_bits, sizeof(uint32_t) * ((Hg + 31) / 32), 0, s);  // DERIVED: k_ae_claim sets and clears them in one launch: zero between rounds
     }
-    if (p->fd_handoff_shared) TAKE(d.fdq, sizeof(gx_fd_msg) * H * (d.HQ ? d.HQ : 1));
+    if (p->fd_handoff_shared) TAKE(GX_CK_FDQ, d.fdq, sizeof(gx_fd_msg) * H * (d.HQ ? d.HQ : 1));
   }
-  TAKE(e->conv_bad, sizeof(unsigned long long));
-  if (e->kprof_n) TAKE(d.kprof, sizeof(unsigned long long) * e->kprof_n, 0, s);
-  TAKE(e->digest_buf, sizeof(uint64_t) * H);
+  TAKE(DERIVED, e->conv_bad, sizeof(unsigned long long));  // DERIVED: gx_converged zeroes it before its kernel
+  if (e->kprof_n) TAKE(DERIVED, d.kprof, sizeof(unsigned long long) * e->kprof_n, 0, s);  // DERIVED: diagnostics
+  TAKE(DERIVED, e->digest_buf, sizeof(uint64_t) * H);  // DERIVED: k_digest writes it before gx_host_digests copies it out
   if (d.G > 1) {
-    TAKE(e->ob_entries, sizeof(uint32_t) * H * K);
-    TAKE(d.in_stamp, sizeof(uint32_t) * Hg * K, 0, s);
-    TAKE(e->ob_total, sizeof(uint32_t));
-    TAKE(e->ob_claim, sizeof(uint32_t) * (XPLAN_GMAX + 1), 0, s);
-    if (p->probe_piggyback) TAKE(d.probe_x, sizeof(unsigned long long) * 2, 0, s);
-    TAKE(e->ob_counts, sizeof(uint32_t) * d.G * (1 + 2 * ((H * K + 255) / 256)));
+    TAKE(DERIVED, e->ob_entries, sizeof(uint32_t) * H * K);  // DERIVED: outbox_plan rebuilds it every round before a pack reads it
+    TAKE(GX_CK_IN_STAMP, d.in_stamp, sizeof(uint32_t) * Hg * K, 0, s);
+    TAKE(DERIVED, e->ob_total, sizeof(uint32_t));  // DERIVED: k_ob_bytes writes it before k_outbox_pack reads it
+    TAKE(DERIVED, e->ob_claim, sizeof(uint32_t) * (XPLAN_GMAX + 1), 0, s);  // DERIVED: the last block of a packing k_send resets it: zero between rounds
+    if (p->probe_piggyback) TAKE(GX_CK_PROBE_X, d.probe_x, sizeof(unsigned long long) * 2, 0, s);
+    TAKE(DERIVED, e->ob_counts, sizeof(uint32_t) * d.G * (1 + 2 * ((H * K + 255) / 256)));  // DERIVED: outbox_plan rebuilds it every round
     const size_t np = Hg / 2 + 1;
-    TAKE(e->ae_pa, sizeof(uint32_t) * np);
-    TAKE(e->ae_pb, sizeof(uint32_t) * np);
-    TAKE(e->ae_prow, sizeof(int32_t) * np);
-    TAKE(e->ae_pcount, np);
-    TAKE(e->ae_pack_host, sizeof(uint32_t) * np);
-    TAKE(e->ae_pack_t, sizeof(uint32_t) * np);
-    TAKE(e->ae_pack_other, sizeof(uint32_t) * np);
-    TAKE(e->ae_pack_first, np);
-    TAKE(e->ae_skip, np);
-    if (pp_state(d)) TAKE(e->fd_rsnap, sizeof(uint64_t) * np * Hg);
-    TAKE(e->ae_dig, sizeof(ulonglong2) * H * e->nblk);
-    TAKE(e->ae_mask, sizeof(uint32_t) * H * e->nmw);
-    TAKE(e->ae_fmask, sizeof(uint32_t) * H * e->nmw);
-    TAKE(e->ae_lt, sizeof(uint16_t) * H * e->nblk);
-    TAKE(e->ae_retL, sizeof(uint16_t) * H * e->nblk);
-    TAKE(e->ae_bcnt, sizeof(uint32_t) * H * e->nblk);
-    TAKE(e->ae_cnt, sizeof(uint32_t) * H);
-    TAKE(e->ae_nfol, sizeof(uint32_t) * H);
-    TAKE(e->ae_sz, sizeof(uint64_t) * 4 * H);
-    TAKE(e->ae_off, sizeof(uint64_t) * 4 * H);
-    TAKE(e->ae_rioff, sizeof(uint64_t) * H);
-    TAKE(e->ae_err, sizeof(uint32_t));
+    TAKE(DERIVED, e->ae_pa, sizeof(uint32_t) * np);  // DERIVED: the push-pull chain (gx_ae_bytes) plans it anew every step
+    TAKE(DERIVED, e->ae_pb, sizeof(uint32_t) * np);  // DERIVED: as ae_pa
+    TAKE(DERIVED, e->ae_prow, sizeof(int32_t) * np);  // DERIVED: as ae_pa
+    TAKE(DERIVED, e->ae_pcount, np);  // DERIVED: as ae_pa
+    TAKE(DERIVED, e->ae_pack_host, sizeof(uint32_t) * np);  // DERIVED: as ae_pa
+    TAKE(DERIVED, e->ae_pack_t, sizeof(uint32_t) * np);  // DERIVED: as ae_pa
+    TAKE(DERIVED, e->ae_pack_other, sizeof(uint32_t) * np);  // DERIVED: as ae_pa
+    TAKE(DERIVED, e->ae_pack_first, np);  // DERIVED: as ae_pa
+    TAKE(DERIVED, e->ae_skip, np);  // DERIVED: as ae_pa
+    if (pp_state(d)) TAKE(DERIVED, e->fd_rsnap, sizeof(uint64_t) * np * Hg);  // DERIVED: received with the step's digests before the merge reads it
+    TAKE(DERIVED, e->ae_dig, sizeof(ulonglong2) * H * e->nblk);  // DERIVED: the step's digest pass writes it
+    TAKE(DERIVED, e->ae_mask, sizeof(uint32_t) * H * e->nmw);  // DERIVED: the step's mask pass writes it
+    TAKE(DERIVED, e->ae_fmask, sizeof(uint32_t) * H * e->nmw);  // DERIVED: as ae_mask
+    TAKE(DERIVED, e->ae_lt, sizeof(uint16_t) * H * e->nblk);  // DERIVED: as ae_mask
+    TAKE(DERIVED, e->ae_retL, sizeof(uint16_t) * H * e->nblk);  // DERIVED: the step's return pass writes it
+    TAKE(DERIVED, e->ae_bcnt, sizeof(uint32_t) * H * e->nblk);  // DERIVED: as ae_dig
+    TAKE(DERIVED, e->ae_cnt, sizeof(uint32_t) * H);  // DERIVED: as ae_mask
+    TAKE(DERIVED, e->ae_nfol, sizeof(uint32_t) * H);  // DERIVED: as ae_mask
+    TAKE(DERIVED, e->ae_sz, sizeof(uint64_t) * 4 * H);  // DERIVED: the step's size passes write it
+    TAKE(DERIVED, e->ae_off, sizeof(uint64_t) * 4 * H);  // DERIVED: the step's scans write it
+    TAKE(DERIVED, e->ae_rioff, sizeof(uint64_t) * H);  // DERIVED: as ae_off
+    TAKE(DERIVED, e->ae_err, sizeof(uint32_t));  // DERIVED: each chain call zeroes it before its kernels
     if (p->lock_readers) {
-      TAKE(e->ae_rov, np, 0, s);
-      TAKE(e->ro_xc, sizeof(unsigned long long) * 3, 0, s);
+      TAKE(DERIVED, e->ae_rov, np, 0, s);  // DERIVED: k_ae_mask writes each planned pair's verdict before the step reads it
+      TAKE(GX_CK_RO_XC, e->ro_xc, sizeof(unsigned long long) * 3, 0, s);
     }
   }
   return GX_OK;
 }
 #undef TAKE
+#undef DERIVED
 
 static int create_init(gx_engine *e) {
   Dev &d = e->d;
@@ -1472,6 +1501,7 @@ static size_t slot_bytes(const Dev &d) {
 int gx_round_send(gx_engine *e) {
   if (!e) return GX_EINVAL;
   GXTRY(enter(e, ENTRY_PHASE));
+  e->round_open = true;
   int rc = round_send_impl(e);
   return rc ? rc : phase_done(e);
 }
@@ -1662,6 +1692,7 @@ int gx_round_end(gx_engine *e) {
   int rc = join_side(e);
   if (rc) return rc;
   GXTRY(watch_round_end(e));
+  e->round_open = false;
   e->pp_cursor = 0;
   rc = wake_all(e);
   return rc ? rc : phase_done(e);
@@ -1677,6 +1708,7 @@ static bool send_packs(const Dev &d) {
 int gx_round_gossip_begin(gx_engine *e, uint64_t *plan, void *buf, uint64_t cap) {
   if (!e || !plan || (cap && !buf)) return GX_EINVAL;
   Dev &d = e->d;
+  e->round_open = true;
   if (!send_packs(d)) {
     int rc = gx_round_send(e);
     if (!rc) rc = gx_exchange_plan(e, plan);
@@ -1721,6 +1753,9 @@ int gx_round_gossip_end(gx_engine *e, const void *buf, uint64_t bytes, int *ae) 
 
 // a sharded engine's push-pull chain: gx_ae_bytes .. gx_ae_merge, gx_ae_claim_*, gx_ae_skip_locked
 #include "gx_ae_chain_host.hpp"
+
+// engine checkpoints of include/gx_ckpt.h: gx_ckpt_save, gx_ckpt_params, gx_ckpt_load
+#include "gx_ckpt_host.hpp"
 
 // full-state JSON codec: gx_set_names, gx_local_state_json, gx_decode_state_json,
 // gx_merge_remote_state_json

@@ -15,6 +15,7 @@ writes them as device memory.
 """
 from __future__ import annotations
 
+import os
 from itertools import accumulate
 from typing import List
 
@@ -80,8 +81,8 @@ class WireBytes:
 
 
 class _Shard:
-    def __init__(self, params: GxParams, lib, device: torch.device):
-        self.e = Engine(params, lib=lib)
+    def __init__(self, params: GxParams, lib, device: torch.device, engine: Engine = None):
+        self.e = engine if engine is not None else Engine(params, lib=lib)  # a ready engine: ShardRounds.load
         self.device = device
         if device.type == "cuda":
             # the engine queues its work on torch's stream, so packing, the collectives and
@@ -105,11 +106,18 @@ class ShardRounds:
       _reduce(t, op) an int64 tensor of one row per held shard -> its _fold over all G shards
     Engine methods are looked up at each call (tests and profiling tools patch them)."""
 
-    def __init__(self, lib, G: int, ids, device, kw):
+    def __init__(self, lib, G: int, ids, device, kw, engines=None):
+        """engines: the held shards' engines, ready made (restored from checkpoints, `_load_engines`),
+        in the order of `ids`; else each is created from `kw`."""
         self.device = torch.device(device)
         self.G = G
         self.shards: List[_Shard] = []
-        for g in ids:
+        for i, g in enumerate(ids):
+            if engines is not None:
+                e = engines[i]
+                assert max(1, e.params.n_shards) == G and (e.params.shard_id if G > 1 else 0) == g
+                self.shards.append(_Shard(e.params, lib, self.device, engine=e))
+                continue
             p = default_params(lib, **kw)
             p.n_shards = G
             p.shard_id = g
@@ -132,6 +140,26 @@ class ShardRounds:
     @property
     def engines(self) -> List[Engine]:
         return [s.e for s in self.shards]
+
+    # checkpoints (include/gx_ckpt.h): one file per held shard, no collective. The driver's own state
+    # (the planned exchange's buffers and matrix, diagnostics) is derived and starts fresh on a load.
+    @staticmethod
+    def shard_file(dirname, g: int, G: int) -> str:
+        return os.path.join(os.fspath(dirname), f"shard_{g:03d}_of_{G:03d}.gxck")
+
+    def save(self, dirname) -> List[dict]:
+        """Every held shard's checkpoint into `dirname` (between rounds: run_rounds has returned);
+        each file's gx_ckpt_info."""
+        os.makedirs(dirname, exist_ok=True)
+        return [e.ckpt_save(self.shard_file(dirname, e.params.shard_id if self.G > 1 else 0, self.G))
+                for e in self.engines]
+
+    @classmethod
+    def _load_engines(cls, lib, dirname, G: int, ids, device, override) -> List[Engine]:
+        device = torch.device(device)
+        if device.type == "cuda":
+            override = dict(override, device=device.index or 0)
+        return [Engine.from_checkpoint(cls.shard_file(dirname, g, G), lib=lib, **override) for g in ids]
 
     def _exchange_sized(self, rows, pack, after_pack=None):
         """One exchange whose sizes the shards report (`rows`); pack(i, ptr, cap) fills held shard
@@ -330,6 +358,19 @@ class LocalShards(ShardRounds):
     def __init__(self, lib, G: int, device="cpu", **kw):
         super().__init__(lib, G, range(G), device, kw)
 
+    @classmethod
+    def load(cls, lib, dirname, device="cpu", **override) -> "LocalShards":
+        """The cluster `save` wrote into `dirname`: every shard file found there (shard 0's name tells
+        G). override: as Engine.from_checkpoint, applied to every shard."""
+        names = [n for n in sorted(os.listdir(dirname)) if n.startswith("shard_000_of_") and n.endswith(".gxck")]
+        if len(names) != 1:
+            raise FileNotFoundError(f"no single shard_000_of_*.gxck in {dirname}")
+        G = int(names[0][len("shard_000_of_"):-len(".gxck")])
+        self = cls.__new__(cls)
+        ShardRounds.__init__(self, lib, G, range(G), device, None,
+                             engines=cls._load_engines(lib, dirname, G, range(G), device, override))
+        return self
+
     def _matrix(self, rows) -> List[List[int]]:
         if isinstance(rows[0], torch.Tensor):
             return torch.stack(rows).tolist()  # device rows: the one host wait of the exchange
@@ -349,17 +390,24 @@ class DistShard(ShardRounds):
 
     CHUNK = 256 << 20  # bytes per peer per all-to-all call
 
-    def __init__(self, lib, rank: int, world: int, device, group=None, **kw):
+    def __init__(self, lib, rank: int, world: int, device, group=None, _engines=None, **kw):
         import torch.distributed as dist
         self.dist = dist
         self.group = group
         self.rank, self.world = rank, world
-        super().__init__(lib, world, [rank], device, kw)
+        super().__init__(lib, world, [rank], device, kw, engines=_engines)
         self.e = self.shards[0].e
         # gloo has no device all-to-all / all-gather: a gloo group over device shards (the one-GPU
         # rehearsal of the RCCL path in tests/test_gpu_dist.py) stages collectives through the host
         self.stage = self.device.type == "cuda" and dist.get_backend(group) == "gloo"
         self._precv = torch.empty(0, dtype=torch.uint8, device=self.device)  # the planned move's inbox
+
+    @classmethod
+    def load(cls, lib, dirname, rank: int, world: int, device, group=None, **override) -> "DistShard":
+        """This rank's shard of the cluster `save` wrote into `dirname` (every rank wrote its own file
+        there); no collective. override: as Engine.from_checkpoint."""
+        return cls(lib, rank, world, device, group=group,
+                   _engines=cls._load_engines(lib, dirname, world, [rank], device, override))
 
     def _host(self, t: torch.Tensor) -> torch.Tensor:
         return t.cpu() if self.stage else t
