@@ -290,15 +290,25 @@ class ShardRounds:
         for e in es:
             e.round_end()
 
-    def run_rounds(self, n: int):
+    def round_gossip(self) -> bool:
+        """The gossip half of one round: send, exchange, merge. True in a push-pull round, whose
+        views then stand as the push-pull steps will read them; round_finish() ends the round."""
         planned = planned_exchange(self.shards[0].e.params)  # sizes from the seeded plan: no host wait
+        self.exchange_paths["planned" if planned else "sized"] += 1
+        return self._gossip_planned() if planned else self._gossip_sized()
+
+    def round_finish(self, ae: bool):
+        """The rest of the round round_gossip() began (`ae`: what it returned): the push-pull steps
+        and the round's end."""
+        if ae:
+            self._push_pull()
+        elif not planned_exchange(self.shards[0].e.params):  # the planned gossip's end call ended the round
+            for s in self.shards:
+                s.e.round_end()
+
+    def run_rounds(self, n: int):
         for _ in range(n):
-            self.exchange_paths["planned" if planned else "sized"] += 1
-            if self._gossip_planned() if planned else self._gossip_sized():
-                self._push_pull()
-            elif not planned:
-                for s in self.shards:
-                    s.e.round_end()
+            self.round_finish(self.round_gossip())
 
     def watch_arm(self, n: int, log_rounds: int = 0):
         """A record watch on every held shard (include/gx_watch.h): each counts its own views."""
