@@ -510,6 +510,21 @@ GXD uint32_t quiet_term(const Dev &d, uint32_t vi, const gx_host_state &hs) {
   const uint64_t b = (uint64_t)d.round + 1u + (dist + kg) / kg;  // ceil((dist + 1) / kg)
   return b < 0xfffffffeull ? (uint32_t)b : 0xfffffffeu;
 }
+// A batch of quiet rounds in one k_send launch: Dev's per-round fields moved on to the
+// next round, as the host's set_round_fields would set them for it. `partitioned` is derived here,
+// so a batch may cross the partition's boundaries (it only changes the sampled peer count there).
+GXD void next_round_fields(Dev &d) {
+  d.round++;
+  d.now = d.p.t0_ns + d.round * d.p.round_ns;
+  d.partitioned = d.round >= d.p.partition_start && d.round < d.p.partition_end;
+  uint32_t *const ic = d.in_cnt, *const wl = d.wl_cnt, *const ov = d.ovf_cnt;
+  d.in_cnt = d.in_cnt_nx;
+  d.in_cnt_nx = ic;
+  d.wl_cnt = d.wl_cnt_nx;
+  d.wl_cnt_nx = wl;
+  d.ovf_cnt = d.ovf_cnt_nx;
+  d.ovf_cnt_nx = ov;
+}
 GXD void note_locked(const Dev &d) { atomicMin(&d.ctr->first_drop[shard_id()][1], (unsigned long long)d.round); }
 
 // --------------------------------------------------- change bookkeeping --

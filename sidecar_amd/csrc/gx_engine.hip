@@ -206,6 +206,7 @@ struct gx_engine {
   int64_t quiet_until, quiet_from;
   bool quiet_now;
   bool quiet_send = true;  // quiet rounds launch k_send's lean instance (env GX_QUIET_SEND=0: the generic one, for A/B runs)
+  uint32_t quiet_batch;    // quiet rounds one launch of it runs at the most (quiet_batch_len; env GX_QUIET_BATCH, 1: a launch per round)
   uint32_t *in_cnt_buf;     // [2][Hl] inbox counts by round parity (Dev::in_cnt, in_cnt_nx)
   int async_phases;         // sharded phase calls return without waiting (gx_set_stream)
   int device;
@@ -646,27 +647,28 @@ struct SendSel {
 // it one (k_send's static_asserts state the same). Lean and generic instance give identical results.
 // 4 lanes per host: measured best of 1/4/8/16/64 (profiles/send_team.sh);
 // teams of 2 / 8 lanes measured 25.6 / 28.7 vs 21.1 us (profiles/r02/gossip/send_team_ab.log)
-static void launch_send(gx_engine *e, SendSel sel, int do_bt) {
+// nr: the quiet rounds the launch runs (a batch, run_quiet_batch); only the lean instance takes more than 1.
+static void launch_send(gx_engine *e, SendSel sel, int do_bt, int nr) {
   const Dev &d = e->d;
   const unsigned g = nblk(d.Hl, 64);
   hipStream_t s = e->stream;
   if (sel.quiet && sel.plan && !ev_of(e)) {
     if (!sel.scan) {
-      k_send<4, false, false, false, false, 0, true, true><<<g, 256, 0, s>>>(d, do_bt);
+      k_send<4, false, false, false, false, 0, true, true><<<g, 256, 0, s>>>(d, do_bt, nr);
       return;
     }
     with_flag(vec_of(e), [&](auto V) {
-      with_own(sel.own, [&](auto O) { k_send<4, false, true, V(), false, O(), true, true><<<g, 256, 0, s>>>(d, do_bt); });
+      with_own(sel.own, [&](auto O) { k_send<4, false, true, V(), false, O(), true, true><<<g, 256, 0, s>>>(d, do_bt, nr); });
     });
     return;
   }
   auto rest = [&](auto X, auto P) {
     if (!sel.scan) {
-      k_send<4, X(), false, false, false, 0, P()><<<g, 256, 0, s>>>(d, do_bt);
+      k_send<4, X(), false, false, false, 0, P()><<<g, 256, 0, s>>>(d, do_bt, 1);
       return;
     }
     with_flags(vec_of(e), ev_of(e), [&](auto V, auto E) {
-      with_own(sel.own, [&](auto O) { k_send<4, X(), true, V(), E(), O(), P()><<<g, 256, 0, s>>>(d, do_bt); });
+      with_own(sel.own, [&](auto O) { k_send<4, X(), true, V(), E(), O(), P()><<<g, 256, 0, s>>>(d, do_bt, 1); });
     });
   };
   if (sel.plan) rest(std::false_type{}, std::true_type{});
@@ -674,15 +676,22 @@ static void launch_send(gx_engine *e, SendSel sel, int do_bt) {
 }
 
 // Phases 0-3 (wake, owners, expiry scan, storm, GetBroadcasts) for this engine's hosts.
-static int round_send_impl(gx_engine *e) {
+// nr > 1: the quiet rounds [d.round, d.round + nr) in these launches (run_quiet_batch, which has checked
+// them): the owner, scan and send launches of the first, whose k_send runs the others' ticks and
+// sends itself. Such a launch carries no snapshot: no view is scanned in those rounds, and the bound
+// it would report is read from the half of Dev::quiet_w that its own last round rewrites when nr is even.
+static int round_send_impl(gx_engine *e, int nr = 1) {
   Dev &d = e->d;
   set_round_fields(e);
   InRound in_round_guard(d);
-  {
+  if (nr > 1) {
+    d.snap = nullptr;
+    quiet_take(e);
+  } else {
     int rc = scan_probe_begin(e);
     if (rc) return rc;
+    if (quiet_params(d)) quiet_probe(e);
   }
-  if (quiet_params(d)) quiet_probe(e);
   d.n_remote = 0;
   hipStream_t s = e->stream;
   if (d.p.probe_piggyback) {  // the probe ping and ack calls come before the owner phase (gx.h)
@@ -740,7 +749,7 @@ static int round_send_impl(gx_engine *e) {
   {
     LaunchTimer t(e, GX_K_SEND);
     if (d.p.fd_enable) k_fd_send<<<nblk(d.Hl, 64), 64, 0, s>>>(d);  // memberlist's targets + messages
-    launch_send(e, sel, bt_apart ? 0 : 1);
+    launch_send(e, sel, bt_apart ? 0 : 1, sel.quiet ? nr : 1);
   }
   HIPCHK(hipGetLastError());
   return scan_probe_end(e);
@@ -1041,6 +1050,59 @@ static int run_one_round(gx_engine *e) {
   return rc;
 }
 
+// A batch of quiet rounds: how many rounds from d.round on, `left` at the most, one
+// k_send launch may run. Each must be quiet by a bound already taken (quiet_until), none the storm's,
+// with no listener and no record watch (its counts are per round); the lean instance must be in use,
+// and a push-pull round of GX_PP_INITIATE mode ends the batch before it (its batches launch in quiet
+// rounds too, ae_whole_impl). Fewer than 2: the round runs alone (run_one_round).
+#ifndef GX_QUIET_BATCH
+#define GX_QUIET_BATCH 32
+#endif
+static uint32_t quiet_batch_len(gx_engine *e, uint32_t left) {
+  Dev &d = e->d;
+  if (e->quiet_batch < 2 || left < 2 || !e->quiet_send || !quiet_params(d) || !e->log_views.empty() || e->watch.n) return 1;
+  quiet_take(e);
+  const int64_t r0 = d.round;
+  if (r0 >= e->quiet_until) return 1;
+  uint32_t n = (uint32_t)std::min<int64_t>({(int64_t)left, (int64_t)e->quiet_batch, e->quiet_until - r0});
+  for (uint32_t j = 0; j < n; j++) {
+    d.round = r0 + j;
+    const bool storm = d.p.storm_round >= 0 && d.round == d.p.storm_round;
+    if (storm || (d.p.push_pull_mode == GX_PP_INITIATE && ae_round(e))) n = j;
+  }
+  d.round = r0;
+  return n < 2 ? 1 : n;
+}
+// Runs it: the first round's launches with the round count, then the push-pull rounds among them,
+// which in a quiet round are only their counts (ae_whole_impl): one note with the pairs of all of
+// them, at the round of the first (the first locked round it may set), then the round number moves.
+static int run_quiet_batch(gx_engine *e, uint32_t n) {
+  Dev &d = e->d;
+  int rc = round_send_impl(e, (int)n);
+  e->quiet_now = false;
+  if (rc) return rc;
+  const int64_t r0 = d.round;
+  int64_t first = -1;
+  uint32_t pairs = 0;
+  for (uint32_t j = 0; j < n; j++) {
+    d.round = r0 + j;
+    if (!ae_round(e)) continue;
+    set_round_fields(e);  // the matching draws inside a partition's side
+    const uint32_t np = ae_matching(d).np;
+    if (np && first < 0) first = d.round;
+    pairs += np;
+  }
+  if (pairs) {
+    d.round = first;
+    set_round_fields(e);
+    LaunchTimer t(e, GX_K_AE);
+    k_ae_locked_note<<<1, 64, 0, e->stream>>>(d, pairs, 1u);
+  }
+  d.round = r0 + n;
+  HIPCHK(hipGetLastError());
+  return GX_OK;
+}
+
 static int wake_all(gx_engine *e) {
   set_round_fields(e);
   k_wake<<<nblk(e->d.Hl, 64), 64, 0, e->stream>>>(e->d);
@@ -1265,6 +1327,8 @@ static void create_dims(gx_engine *e, const gx_params *p) {
   if (getenv("GX_KPROF"))  // diagnostics: phase marks of every k_send wave (gx_kprof_read)
     e->kprof_n = (size_t)nblk(d.Hl, 64) * 4 * 8 + GX_KPROF_MERGE_N + 3ull * d.H;  // + merge counts + push-pull blocks + scans
   if (const char *qs = getenv("GX_QUIET_SEND")) e->quiet_send = strcmp(qs, "0") != 0;
+  e->quiet_batch = GX_QUIET_BATCH;
+  if (const char *qb = getenv("GX_QUIET_BATCH")) e->quiet_batch = (uint32_t)std::min(std::max(atol(qb), 1l), 1024l);
   if (d.G > 1) {
     e->nblk = d.nblk_ae;
     e->nmw = (e->nblk + 31) / 32;
@@ -1472,9 +1536,11 @@ int gx_run_rounds(gx_engine *e, uint32_t n_rounds) {
   if (!e || e->d.G > 1 || e->d.round + n_rounds >= GX_MAX_ROUND) return GX_EINVAL;
   GXTRY(enter(e, ENTRY_ROUNDS));
   e->quiet_nowait = false;
-  for (uint32_t i = 0; i < n_rounds; i++) {
-    int rc = run_one_round(e);
+  for (uint32_t i = 0; i < n_rounds;) {
+    const uint32_t nb = quiet_batch_len(e, n_rounds - i);
+    int rc = nb > 1 ? run_quiet_batch(e, nb) : run_one_round(e);
     if (rc) return rc;
+    i += nb;
     if (e->pending_ev.size() > 4096) {
       rc = drain_timing(e);
       if (rc) return rc;

@@ -2004,9 +2004,61 @@ GXD bool filt_used(const Dev &d, uint32_t pos) { return d.sfilt && pos != 0xffff
 // Their only readers are the outbox kernels of a sharded engine (ob_dest, pack_slot), and quiet
 // rounds need one shard (quiet_params), where every entry that launches them returns first.
 #define PLAN_PEERS(QUIET) ((QUIET) ? 0 : PLAN_CH)  // the team's peers slot behind its chunk plans (none kept in LDS when QUIET)
+// The owner phase of host idx in a quiet round after the first of a batch (k_send QUIET with a round
+// count), on the team's register copy `hs`, by the team; d holds that round's fields.
+// What owner_tick does for a host that holds the lock with a looper blocked: the due sleepers re-enter
+// the FIFO, churn draws, and neither looper ticks (both conditions fail on the set flag under
+// lock_model 1), so no view is read. Its stores of zeros (in_cnt_nx, tick, the next round's list
+// counts) are left out: the batch's first round zeroed the one buffer and nothing of a quiet round
+// writes the other. As there, the sleep ring's head and (FWD) the FIFO head jobs load in one round
+// trip while the lead lane samples the round's peers (only their count matters to the lean sends).
+// Returns the FIFO head jobs loaded into pj (from hs.fifo_head on).
+template <int T, bool FWD, int SW>
+GXD uint32_t quiet_tick(const Dev &d, Acc &a, uint32_t idx, gx_host_state &hs, gx_sleeper *sj, gx_job *pj,
+                        uint32_t *peers) {
+  const uint32_t tl = threadIdx.x & (T - 1), o = d.lo + idx;
+  const bool lead = tl == 0;
+  const uint32_t win = d.NG > 1 ? (uint32_t)SW : (uint32_t)T;
+  {
+    const uint32_t ns = hs.sleep_tail - hs.sleep_head;
+    for (uint32_t x = tl; x < ns && x < win; x += T) sj[x] = d.sleep[(size_t)idx * d.SQ + ((hs.sleep_head + x) & (d.SQ - 1u))];
+  }
+  uint32_t npf = 0;
+  if (FWD) {  // stored jobs only: the re-arms below push at the tail
+    const uint32_t q = hs.fifo_stored - hs.fifo_head, pw = pj_window<T>(d);
+    npf = q < pw ? q : pw;
+    for (uint32_t x = tl; x < npf; x += T) pj[x] = d.fifo[(size_t)idx * d.Q + ((hs.fifo_head + x) % d.Q)];
+  }
+  if (lead) peers[16] = sample_peers_h(d, peer_seed(d), o, peers);
+  wave_sync();  // the team's sleep-ring and job slots, the peer count
+  for (uint32_t w = 0; hs.sleep_head != hs.sleep_tail; w++) {
+    if (w == win) {
+      const uint32_t ns = hs.sleep_tail - hs.sleep_head;
+      wave_sync();
+      for (uint32_t x = tl; x < ns && x < win; x += T) sj[x] = d.sleep[(size_t)idx * d.SQ + ((hs.sleep_head + x) & (d.SQ - 1u))];
+      wave_sync();
+      w = 0;
+    }
+    const gx_sleeper z = sj[w];
+    if ((int64_t)z.wake > d.round) break;
+    hs.sleep_head++;
+    push_job_r(d, a, o, hs, z.job, lead);
+  }
+  if (d.p.churn_ppm) {  // discovery churn: one service starts or stops
+    const uint64_t x = rng4(d.p.seed, ST_CHURN, (uint64_t)d.round, o, 0);
+    if ((uint32_t)(x & 0xffffffffu) % 1000000u < d.p.churn_ppm) {
+      const uint32_t cs = (uint32_t)((x >> 32) % d.S);
+      hs.running ^= 1ull << cs;
+      if (lead && ((hs.running >> cs) & 1ull)) d.own_status[(size_t)idx * d.S + cs] = GX_ALIVE;
+      if (lead) a.c[C_CHURN]++;
+    }
+  }
+  return npf;
+}
 template <int T, bool X, bool PLAN = false, bool FWD = false, bool QUIET = false>
 GXD void send_host(const Dev &d, Acc &a, uint32_t idx, gx_job *pjs, int do_bt, unsigned &lost, PlanCall *pl,
-                   unsigned long long &kb, unsigned long long &kl, const TickFwd &fwd, uint32_t &quiet) {
+                   unsigned long long &kb, unsigned long long &kl, const TickFwd &fwd, uint32_t &quiet,
+                   gx_sleeper *sj = nullptr, int nr = 1, uint32_t *lkr = nullptr) {
   const uint32_t lane = threadIdx.x & (T - 1);
   {
     uint32_t u = d.lo + idx;
@@ -2042,11 +2094,36 @@ GXD void send_host(const Dev &d, Acc &a, uint32_t idx, gx_job *pjs, int do_bt, u
     GX_KP(4);
     if (PLAN) {
       uint32_t *peers = reinterpret_cast<uint32_t *>(&pl[PLAN_PEERS(QUIET)]);  // the team's peers (k_send's prologue)
-      const uint32_t np = peers[16];
-      send_planned<T, QUIET>(d, a, idx, hs, pjs, pl, peers, np, kb, kl, (pre && fwd.pf0 == hs.fifo_head) ? fwd.npf : 0u);
-      hs.lock = lock_snap(hs.lock, hs.flags, d.round + 1, d.p.lock_readers != 0);  // the lock for the next round
-      if (lane == 0) *h = hs;
-      if (lane == 0 && d.p.lock_model) quiet = quiet_term(d, idx, hs);  // (planned sends only: the other paths fold 0)
+      if constexpr (QUIET) {
+        // The quiet rounds [d.round, d.round + nr) of a batch, one after another: nothing
+        // of a quiet round reads or writes another host's state, so the team runs ahead of the grid on
+        // its register copy of the bookkeeping, stored once. dr: Dev with the running round's fields.
+        // Between two rounds a fence and a wave sync: the later round's lanes read sleepers, FIFO jobs
+        // and ring records that the lead lane (the ring: lane p % T) stored in the earlier one.
+        Dev dr = d;
+        uint32_t npf = (pre && fwd.pf0 == hs.fifo_head) ? fwd.npf : 0u;
+        for (int i = 0;;) {
+          const bool was = a.locked;
+          send_planned<T, true>(dr, a, idx, hs, pjs, pl, peers, peers[16], kb, kl, npf);
+          hs.lock = lock_snap(hs.lock, hs.flags, dr.round + 1, dr.p.lock_readers != 0);  // the lock for the next round
+          if (a.locked && !was) *lkr = (uint32_t)i;  // the batch's first round whose lock held back work
+          if (++i >= nr) break;
+          next_round_fields(dr);
+          dr.kprof = nullptr;  // the phase marks are the first round's
+          __threadfence_block();
+          wave_sync();
+          npf = quiet_tick<T, FWD, FWD ? T * GX_JPF : T>(dr, a, idx, hs, sj, pjs, peers);  // (SW: k_send's SLW)
+          if (lane == 0) kb += 128;
+        }
+        if (lane == 0) *h = hs;
+        if (lane == 0 && d.p.lock_model) quiet = quiet_term(dr, idx, hs);  // the last round's term
+      } else {
+        const uint32_t np = peers[16];
+        send_planned<T, QUIET>(d, a, idx, hs, pjs, pl, peers, np, kb, kl, (pre && fwd.pf0 == hs.fifo_head) ? fwd.npf : 0u);
+        hs.lock = lock_snap(hs.lock, hs.flags, d.round + 1, d.p.lock_readers != 0);  // the lock for the next round
+        if (lane == 0) *h = hs;
+        if (lane == 0 && d.p.lock_model) quiet = quiet_term(d, idx, hs);  // (planned sends only: the other paths fold 0)
+      }
     } else if (!X || !departed(d, u)) {
       const bool fd = X && d.p.fd_enable;
       uint32_t peers[16];
@@ -2144,10 +2221,12 @@ GXD void send_host(const Dev &d, Acc &a, uint32_t idx, gx_job *pjs, int do_bt, u
 // block scans its queued views and sends. Nothing of one host's tick or send reads another host's
 // state except the receivers' inbox counts, zeroed a round ahead (Dev::in_cnt_nx).
 // QUIET: the lean planned sends of a quiet round (send_planned); the owner ticks and the scan prologue
-// are the generic ones.
+// are the generic ones. nr (QUIET only; the other instances ignore it): the launch runs the quiet rounds
+// [d.round, d.round + nr), each team looping over them by itself (send_host, quiet_tick); the prologue,
+// the owner ticks and the snapshot below belong to the first, the wave's term of the bound to the last.
 template <int T, bool X, bool SCAN = false, bool VEC = false, bool EV = false, int OWN = 0, bool PLAN = false,
           bool QUIET = false>
-__global__ __launch_bounds__(256) void k_send(Dev d, int do_bt) {
+__global__ __launch_bounds__(256) void k_send(Dev d, int do_bt, int nr) {
   // the variants the host builds (launch_send): VEC, EV and OWN only shape the scans and owner ticks
   // that SCAN brings in, planned sends run without departures or the detector, and quiet rounds are
   // planned and have no listener
@@ -2159,7 +2238,10 @@ __global__ __launch_bounds__(256) void k_send(Dev d, int do_bt) {
   __shared__ PlanCall s_pl[PLAN ? 256 / T : 1][PLAN_PEERS(QUIET) + 1];
   __shared__ ScanLds sm;
   __shared__ uint32_t s_scan[256 / T], s_nscan;
-  __shared__ gx_sleeper s_sl[OWN ? 256 * GX_JPF : 1];  // sleep-ring heads of the owner ticks
+  // sleep-ring heads of the owner ticks, SLW per team; QUIET without them: of a batch's later rounds
+  // (quiet_tick; T do, quiet rounds have GossipMessages 1)
+  constexpr int SLW = OWN ? T * GX_JPF : T;
+  __shared__ gx_sleeper s_sl[OWN ? 256 * GX_JPF : QUIET ? 256 : 1];
   Acc a;
   const uint32_t idx = blockIdx.x * (256 / T) + threadIdx.x / T;
   unsigned lost = 0;
@@ -2201,7 +2283,7 @@ __global__ __launch_bounds__(256) void k_send(Dev d, int do_bt) {
       }
     }
     __syncthreads();
-    const bool q = owner_tick<T, OWN, PLAN, T * GX_JPF>(d, a, idx, &s_sl[(threadIdx.x / T) * (T * GX_JPF)], fwd);
+    const bool q = owner_tick<T, OWN, PLAN, T * GX_JPF>(d, a, idx, &s_sl[(threadIdx.x / T) * SLW], fwd);
     if (q) s_scan[atomicAdd(&s_nscan, 1u)] = idx;  // lead lanes only
     GX_KP(1);
     __syncthreads();  // the block's ticks before its scans and sends read them
@@ -2226,16 +2308,25 @@ __global__ __launch_bounds__(256) void k_send(Dev d, int do_bt) {
   // this host's quiet-round term (quiet_term; lead lanes of hosts): a host that sets none folds 0
   uint32_t quiet = idx < d.Hl && (threadIdx.x & (T - 1)) == 0 ? 0u : 0xffffffffu;
   GX_KP(3);
+  uint32_t lkr = 0xffffffffu;  // QUIET: the first round of the batch in which the lock held back work
   if (idx < d.Hl)  // (PLAN runs without departures: every host ticked)
     send_host<T, X, PLAN, PLAN && (OWN > 0), QUIET>(d, a, idx, s_pj[threadIdx.x / T], do_bt, lost,
-                                                   s_pl[PLAN ? threadIdx.x / T : 0], kb, kl, fwd, quiet);
-  GX_KP(7);
+                                                   s_pl[PLAN ? threadIdx.x / T : 0], kb, kl, fwd, quiet,
+                                                   QUIET ? &s_sl[(threadIdx.x / T) * SLW] : nullptr, QUIET ? nr : 1, &lkr);
+  GX_KP(7);  // (QUIET: the end of the batch)
+  if constexpr (QUIET) {  // acc_flush's note with that round, not the batch's first
+    a.locked = false;
+    lkr = wave_min32(lkr);
+    if (lkr != 0xffffffffu && (threadIdx.x & 63) == 0)
+      atomicMin(&d.ctr->first_drop[shard_id()][1], (unsigned long long)(d.round + lkr));
+  }
   acc_flush(d, a);
+  const int64_t rl = QUIET ? d.round + nr - 1 : d.round;  // the round whose terms these are (QUIET: the batch's last)
   if (d.p.lock_model) {  // the wave's term of the round's bound (Dev::quiet_w): a plain store per wave (2048
     // atomicMin on one word cost 18 us per launch at cfg 5, 5 us when only waves that lower it issue one:
     // the waves all finish together; profiles/quiet_rounds/)
     quiet = wave_min32(quiet);
-    if ((threadIdx.x & 63) == 0) d.quiet_w[(size_t)(d.round & 1) * d.QW + blockIdx.x * 4u + (threadIdx.x >> 6)] = quiet;
+    if ((threadIdx.x & 63) == 0) d.quiet_w[(size_t)(rl & 1) * d.QW + blockIdx.x * 4u + (threadIdx.x >> 6)] = quiet;
   }
   if (X && lost) ctr_atomic(d, C_LOST, lost);
   // algorithmic bytes: bookkeeping, FIFO jobs, records read (lists, ring), receiver slots read,
