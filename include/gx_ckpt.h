@@ -29,35 +29,65 @@
  *     u64 checksum of the header with this field 0, followed by the section table
  *     gx_params as the engine was created with (absolute t0_ns), zero-padded to 8 bytes
  *   section table, n_sections entries of 32 bytes, ascending id:
- *     u32 id (GX_CK_*)   u32 coding (GX_CKPT_RAW, GX_CKPT_VIEWS)   u64 raw bytes   u64 stored bytes
+ *     u32 id (GX_CK_*)   u32 coding (GX_CKPT_RAW, _VIEWS, _FIFO)   u64 raw bytes   u64 stored bytes
  *     u64 checksum of the stored bytes
  *   the sections' stored bytes in table order, each zero-padded to 8 bytes (the padding is not
  *   counted in stored bytes and not checksummed)
  * Checksum of n bytes: the bytes as u64 words w[0..ceil(n / 8)) (the last zero-padded); with
  *   m(i) = w[i] ^ ((i + 1) * 0x9E3779B97F4A7C15),  m ^= m >> 32,  m *= 0xD6E8FEB86659FD93,  m ^= m >> 32
  * the checksum is (sum of m(i) mod 2^64) ^ n. Every single changed word changes it.
- * Every section is stored raw (the buffer's bytes) except the views.
+ * gx_ckpt_save stores every section raw (the buffer's bytes) except the views; gx_ckpt_save_coded
+ * may also code the server times (GX_CKPT_CODE_SRVT) and the broadcast FIFOs (GX_CKPT_CODE_FIFO).
+ * The table admits exactly these (id, coding) pairs: GX_CKPT_RAW with any id, GX_CKPT_VIEWS with
+ * GX_CK_VIEW or GX_CK_SRVT, GX_CKPT_FIFO with GX_CK_FIFO.
  *
- * VIEW SECTION (coding GX_CKPT_VIEWS; raw bytes = 8 * Hl * R). R = n_hosts * n_services slots per
- * view, Hl views (this engine's hosts, departed ones included), nblk = ceil(R / 512) blocks of
- * GX_DIGEST_SLOTS slots. First base[R] (u64): base[r] = the unsigned maximum of word r over the Hl
- * views. Then one record per view in ascending view order:
- *     u64 n_lit                      literals of this view; UINT64_MAX = stored raw: R words follow, nothing else
+ * ROW CODING (coding GX_CKPT_VIEWS; raw bytes = 8 * rows * W): a table of `rows` rows of W u64 words,
+ * nblk = ceil(W / 512) blocks of GX_DIGEST_SLOTS slots per row. Two sections instantiate it:
+ *     GX_CK_VIEW  the VIEW SECTION: W = R = n_hosts * n_services slots, rows = Hl views (this engine's
+ *                 hosts, departed ones included)
+ *     GX_CK_SRVT  the SERVER TIMES, gx_server_times [Hl][n_hosts] read as u64 words: W = 2 * n_hosts
+ *                 (always even), rows = Hl; the times as the engine keeps them, relative to gx_epoch
+ *                 (0 stays 0), as in the raw section
+ * First base[W] (u64): base[r] = the unsigned maximum of word r over the rows. Then one record per
+ * row in ascending row order:
+ *     u64 n_lit                      literals of this row; UINT64_MAX = stored raw: W words follow, nothing else
  *     u64 present[ceil(nblk / 64)]   bit b: block b has a slot that differs from base
- *     u64 mask[8] per present block  bit i: slot 512 b + i < R and word != base[slot]; bits past R are 0
- *     u64 literal per mask bit       the view's words, ascending slot order
- * A view is stored raw exactly when its coded record, 8 * (1 + ceil(nblk / 64) + 8 * present blocks
- * + n_lit) bytes, would not be smaller than 8 * R bytes. A warm cluster's views all equal base: the
- * section is 8 R + Hl * 8 * (1 + ceil(nblk / 64)) bytes.
+ *     u64 mask[8] per present block  bit i: slot 512 b + i < W and word != base[slot]; bits past W are 0
+ *     u64 literal per mask bit       the row's words, ascending slot order
+ * A row is stored raw exactly when its coded record, 8 * (1 + ceil(nblk / 64) + 8 * present blocks
+ * + n_lit) bytes, would not be smaller than 8 * W bytes. A warm cluster's rows all equal base: the
+ * section is 8 W + rows * 8 * (1 + ceil(nblk / 64)) bytes (the server times: 16 n_hosts + Hl * 8 *
+ * (1 + ceil(ceil(2 n_hosts / 512) / 64))).
  *
- * MEMORY. Save and load stream through one staging area on the device (a chunk of view records)
- * and two halves in pinned host memory (one is written to the file or read from it while the other
- * is copied), each the largest piece the engine has and GX_CKPT_STAGE_BYTES at most: 256 MiB on the
- * device and 512 MiB pinned at the most, under the 1 GiB this design was given. A chunk is as many
- * views as fit the area at their worst case, 8 + 8 R bytes each; an engine whose single view record
- * exceeds the area (R > 2^25) is GX_ENOMEM. Beyond that both directions allocate the base row (8 R
- * bytes) and 12 bytes per (view, block) of a chunk on the device, and load the new engine. Nothing
- * proportional to the views is allocated on either side.
+ * FIFO SECTION (coding GX_CKPT_FIFO; raw bytes = 16 * Hl * Q, Q = queue_cap): only each ring's stored
+ * window, the jobs gx_read_queue returns. u32 n[Hl], zero-padded to 8 bytes, then for each host in
+ * ascending order its n[v] jobs of 16 bytes in queue order: ring positions p % Q for p = fifo_head ..
+ * fifo_stored - 1 of the host's gx_host_state. Stored bytes = pad8(4 Hl) + 16 * sum of n. The
+ * positions [fifo_stored, fifo_tail) are counted, not stored, in the ring as in the file. A load
+ * restores the ring slots outside the window as zero: nothing reads a slot outside [fifo_head,
+ * fifo_stored) before a push has written it (the readers are listed in DESIGN.md "Checkpoints").
+ * The file must hold the GX_CK_HS section (the lower id: it is restored first); every n[v] <= Q; n[v]
+ * = fifo_stored - fifo_head (mod 2^32) of the restored hs[v]; table and jobs fill the section
+ * exactly. Anything else is GX_EIO.
+ *
+ * MEMORY. Save and load stream through one staging area on the device (a chunk of records) and two
+ * halves in pinned host memory (one is written to the file or read from it while the other is
+ * copied), each the largest piece the engine has and GX_CKPT_STAGE_BYTES at most: 256 MiB on the
+ * device and 512 MiB pinned at the most, under the 1 GiB this design was given. The three coders
+ * share them, one section at a time:
+ *     views         a chunk is as many views as fit the area at their worst case, 8 + 8 R bytes each
+ *     server times  as many rows as fit at 8 + 8 W bytes each
+ *     FIFOs         as many consecutive hosts as fit with the jobs their counts state; a host's
+ *                   worst case is 16 Q bytes
+ * An engine whose single worst-case record of a coded section exceeds the area (R > 2^25) is
+ * GX_ENOMEM. Beyond that both directions allocate, per row-coded section, the base row (8 W bytes)
+ * and 12 bytes per (row, block) of a chunk on the device; for the FIFOs 12 bytes per host on the
+ * device and 4 per host on the host (the count table and its scan); and load the new engine. Nothing
+ * proportional to the views, the server-time table or the rings is allocated on either side.
+ * The environment variable GX_CKPT_STAGE_BYTES, read at each call, lowers the area and the halves
+ * (it cannot raise them): a multiple of 8, else GX_EINVAL; GX_ENOMEM when it is smaller than one
+ * worst-case record of a section this call codes or decodes. It exists so that tests reach the chunk
+ * seams at small sizes; unset, nothing changes.
  *
  * FORK. gx_ckpt_load's `override` may differ from the saved params only in device, partition_start /
  * partition_end, storm_round, depart_round / depart_ppm, and an event (the partition, the storm, the
@@ -86,6 +116,10 @@ extern "C" {
 #define GX_CKPT_HEADER_BYTES 40u
 #define GX_CKPT_RAW 0u
 #define GX_CKPT_VIEWS 1u
+#define GX_CKPT_FIFO 2u
+/* gx_ckpt_save_coded's mask: the sections coded beside the views */
+#define GX_CKPT_CODE_SRVT 1u /* GX_CK_SRVT in the ROW CODING */
+#define GX_CKPT_CODE_FIFO 2u /* GX_CK_FIFO as a FIFO SECTION */
 #define GX_CKPT_STAGE_BYTES ((uint64_t)256 << 20) /* the device staging area, and each of the two pinned halves */
 #define GX_CKPT_MAX_SECTIONS 64u
 
@@ -116,9 +150,24 @@ typedef struct gx_ckpt_info {
   gx_ckpt_section sections[GX_CKPT_MAX_SECTIONS];
 } gx_ckpt_info;
 
+/* The figures of gx_ckpt_save_coded's coders (gx_ckpt_info's times and counts stay the view
+ * section's). Device times are HIP events around the kernels, summed over the chunks. */
+typedef struct gx_ckpt_coded_info {
+  float srvt_ms, srvt_base_ms, srvt_count_ms, srvt_emit_ms; /* server times: total; base, count + scans, emit */
+  float fifo_ms;                                            /* FIFOs: counts, scan and pack */
+  uint32_t srvt_rows_raw;                                   /* server-time rows stored raw */
+  uint32_t srvt_chunks, fifo_chunks;                        /* chunks each coder went through */
+  uint64_t fifo_jobs;                                     /* jobs written: the sum of the count table */
+} gx_ckpt_coded_info;
+
 /* Writes the engine's checkpoint to `path` (created or replaced; removed again on failure). GX_EINVAL
  * inside a round or for a null argument, GX_EIO when the file cannot be written, GX_ENOMEM. */
 int gx_ckpt_save(gx_engine *e, const char *path, gx_ckpt_info *info /* may be null */);
+/* gx_ckpt_save with the sections of `code` (a mask of GX_CKPT_CODE_*; any other bit is GX_EINVAL)
+ * coded on the device. code = 0 is gx_ckpt_save: the same file, byte for byte. A bit whose buffer
+ * the engine lacks is ignored. gx_ckpt_load reads either kind of file: the table says how each
+ * section is coded. info and coded may be null. */
+int gx_ckpt_save_coded(gx_engine *e, const char *path, uint32_t code, gx_ckpt_info *info, gx_ckpt_coded_info *coded);
 /* The header alone, no device: the saved params and round. GX_EIO for a file that cannot be read, is
  * short, is no checkpoint or whose header checksum fails; GX_EINVAL for another format version, ABI
  * version or sizeof(gx_params). */
@@ -129,9 +178,10 @@ int gx_ckpt_params(const char *path, gx_params *out, int64_t *round);
  * checked as by gx_ckpt_params, the override by the FORK rule, then each section's size against
  * what gx_create allocated for the params (GX_EINVAL for a file that does not fit) and each
  * section's checksum before its bytes are handed to a kernel (GX_EIO for a short or damaged file).
- * The view decoder checks on the device, bounded by the section's stored size whatever the records
- * say, that every record's shape holds (present bits below nblk, mask bits below R, popcount of the
- * masks = n_lit, the records fill the section exactly); a section that fails is GX_EIO. No engine
+ * The row decoder checks on the device, bounded by the section's stored size whatever the records
+ * say, that every record's shape holds (present bits below nblk, mask bits below W, popcount of the
+ * masks = n_lit, the records fill the section exactly), the FIFO decoder the rules of FIFO SECTION,
+ * every read bounded by the section's end whatever the table says; a section that fails is GX_EIO. No engine
  * is left behind on failure (*out = null). info may be null. */
 int gx_ckpt_load(const char *path, const gx_params *override, gx_engine **out, gx_ckpt_info *info);
 

@@ -250,8 +250,9 @@ ABI_FUNCS = [
 ]
 ALL_OWNERS = 0xFFFFFFFF
 CKPT_MAX_SECTIONS = 64  # include/gx_ckpt.h
-CKPT_RAW, CKPT_VIEWS = 0, 1
-CK_VIEW, CK_SRVT = 1, 27  # section ids (GX_CK_*) the tools name
+CKPT_RAW, CKPT_VIEWS, CKPT_FIFO = 0, 1, 2
+CKPT_CODE_SRVT, CKPT_CODE_FIFO = 1, 2  # gx_ckpt_save_coded's mask (GX_CKPT_CODE_*)
+CK_VIEW, CK_HS, CK_FIFO, CK_SRVT = 1, 3, 4, 27  # section ids (GX_CK_*) the tools name
 # the params a fork may change (gx_ckpt.h FORK)
 CKPT_FORK_FIELDS = ("device", "partition_start", "partition_end", "storm_round", "depart_round", "depart_ppm")
 
@@ -271,6 +272,15 @@ class GxCkptInfo(C.Structure):
         d["sections"] = {s.id: {"coding": s.coding, "raw_bytes": s.raw_bytes, "stored_bytes": s.stored_bytes}
                          for s in self.sections[:min(self.n_sections, CKPT_MAX_SECTIONS)]}
         return d
+
+
+class GxCkptCodedInfo(C.Structure):
+    _fields_ = [("srvt_ms", C.c_float), ("srvt_base_ms", C.c_float), ("srvt_count_ms", C.c_float),
+                ("srvt_emit_ms", C.c_float), ("fifo_ms", C.c_float), ("srvt_rows_raw", C.c_uint32),
+                ("srvt_chunks", C.c_uint32), ("fifo_chunks", C.c_uint32), ("fifo_jobs", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 WATCH_MAX, WATCH_OFF = 1024, 0xFFFFFFFF  # include/gx_watch.h
@@ -366,6 +376,7 @@ def _declare(lib):
         "gx_watch_read": ([vp, u32, u32, vp, vp, P(i64)], i32),
         # include/gx_ckpt.h
         "gx_ckpt_save": ([vp, C.c_char_p, P(GxCkptInfo)], i32),
+        "gx_ckpt_save_coded": ([vp, C.c_char_p, u32, P(GxCkptInfo), P(GxCkptCodedInfo)], i32),
         "gx_ckpt_params": ([C.c_char_p, P(GxParams), P(i64)], i32),
         "gx_ckpt_load": ([C.c_char_p, P(GxParams), P(vp), P(GxCkptInfo)], i32),
     }
@@ -477,12 +488,19 @@ class Engine:
         self.hi = ((gid + 1) * self.H) // self.G
 
     # checkpoints (include/gx_ckpt.h; HIP engine) ---------------------------------------------
-    def ckpt_save(self, path) -> dict:
+    def ckpt_save(self, path, code=0) -> dict:
         """The engine's state between two rounds, to `path`. Returns gx_ckpt_info as a dict: totals,
-        the view coder's device times, and per section id the raw and stored bytes."""
+        the view coder's device times, and per section id the raw and stored bytes. code: a mask of
+        CKPT_CODE_SRVT, CKPT_CODE_FIFO (gx_ckpt_save_coded: the server times and the FIFOs coded on
+        the device); the dict then holds gx_ckpt_coded_info under "coded"."""
         info = GxCkptInfo()
-        check(_ckpt_fn(self.lib, "gx_ckpt_save")(self.h, os.fsencode(path), C.byref(info)), "gx_ckpt_save")
-        return info.as_dict()
+        if not code:
+            check(_ckpt_fn(self.lib, "gx_ckpt_save")(self.h, os.fsencode(path), C.byref(info)), "gx_ckpt_save")
+            return info.as_dict()
+        coded = GxCkptCodedInfo()
+        check(_ckpt_fn(self.lib, "gx_ckpt_save_coded")(self.h, os.fsencode(path), code, C.byref(info), C.byref(coded)),
+              "gx_ckpt_save_coded")
+        return dict(info.as_dict(), coded=coded.as_dict())
 
     @classmethod
     def from_checkpoint(cls, path, lib=None, **override) -> "Engine":

@@ -1,7 +1,7 @@
 // gx_ckpt_file.hpp — the checkpoint file of include/gx_ckpt.h as the host sees it: checksum, header
-// and section table (write, read, check), the fork rule, and the walk over a view section's records.
-// Plain C++ with no device call, so it also builds into a stand-alone host program
-// (tests/cpp/test_ckpt_file.cpp).
+// and section table (write, read, check), the fork rule, the walk over a row-coded section's records
+// and the FIFO section's count table. Plain C++ with no device call, so it also builds into
+// stand-alone host programs (tests/cpp/test_ckpt_file.cpp, tests/cpp/test_ckpt_coded_file.cpp).
 #pragma once
 #include <stdint.h>
 #include <stdio.h>
@@ -82,6 +82,14 @@ static inline std::vector<uint8_t> ck_head_encode(const CkHeader &h) {
   return b;
 }
 
+// The (id, coding) pairs the section table admits (gx_ckpt.h FILE).
+static inline bool ck_coding_admitted(uint32_t id, uint32_t coding) {
+  if (coding == GX_CKPT_RAW) return true;
+  if (coding == GX_CKPT_VIEWS) return id == GX_CK_VIEW || id == GX_CK_SRVT;
+  if (coding == GX_CKPT_FIFO) return id == GX_CK_FIFO;
+  return false;
+}
+
 // Reads and checks header and table (gx_ckpt.h gx_ckpt_params); file_bytes = the file's length: the
 // sections must fill it exactly.
 static inline int ck_head_read(FILE *f, uint64_t file_bytes, CkHeader *h) {
@@ -120,8 +128,11 @@ static inline int ck_head_read(FILE *f, uint64_t file_bytes, CkHeader *h) {
     memcpy(&s.stored, &b[o + 16], 8);
     memcpy(&s.sum, &b[o + 24], 8);
     if (!s.id || s.id >= GX_CK_ID_END || (i && s.id <= h->sec[i - 1].id)) return GX_EINVAL;
-    if (s.coding != GX_CKPT_RAW && !(s.coding == GX_CKPT_VIEWS && s.id == GX_CK_VIEW)) return GX_EINVAL;
+    if (!ck_coding_admitted(s.id, s.coding)) return GX_EINVAL;
     if (s.coding == GX_CKPT_RAW && s.stored != s.raw) return GX_EINVAL;
+    // gx_ckpt.h FIFO SECTION: the counts are checked against the host states of the same file
+    // (ascending ids: GX_CK_HS, if there, is the entry before)
+    if (s.coding == GX_CKPT_FIFO && !(i && h->sec[i - 1].id == GX_CK_HS)) return GX_EIO;
     if (s.stored > file_bytes - at) return GX_EIO;  // a short file (at <= file_bytes throughout)
     s.at = at;
     at += ck_pad8(s.stored);
@@ -155,7 +166,34 @@ static inline int ck_fork_check(const gx_params &saved, const gx_params &o, int6
   return GX_OK;
 }
 
-// A view record at words[0 .. have): its length in words if it is complete and well-formed so far as
+// gx_ckpt.h FIFO SECTION: the count table at `table` (table_bytes of it are there) of a section of
+// `stored` bytes for Hl hosts with rings of Q jobs. The jobs the section holds, or -1 if it can be
+// none: a short table, a count above Q, padding that is not zero, table and jobs that do not fill
+// the section exactly. (That a count equals the host's window is the device's to check.)
+static inline int64_t ck_fifo_table_jobs(const void *table, uint64_t table_bytes, uint64_t Hl, uint64_t Q, uint64_t stored) {
+  const uint64_t tb = ck_pad8(4 * Hl);
+  if (stored < tb || table_bytes < tb || (stored - tb) % 16) return -1;
+  uint64_t jobs = 0;
+  for (uint64_t v = 0; v < tb / 4; v++) {
+    uint32_t n;
+    memcpy(&n, (const uint8_t *)table + 4 * v, 4);
+    if (v >= Hl ? n != 0 : n > Q) return -1;
+    jobs += n;
+  }
+  return jobs == (stored - tb) / 16 ? (int64_t)jobs : -1;
+}
+// The hosts from v0 on whose jobs fit `bytes` of staging together (16 bytes a job); 0 when the
+// first one's alone do not. *jobs = what they hold.
+static inline uint32_t ck_fifo_chunk_hosts(const uint32_t *n, uint32_t v0, uint32_t Hl, uint64_t bytes, uint64_t *jobs) {
+  uint64_t sum = 0;
+  uint32_t v = v0;
+  for (; v < Hl && 16 * (sum + n[v]) <= bytes; v++) sum += n[v];
+  *jobs = sum;
+  return v - v0;
+}
+
+// A row record (gx_ckpt.h ROW CODING; a view's, or a server-time row's with R = W) at
+// words[0 .. have): its length in words if it is complete and well-formed so far as
 // the host can tell (n_lit and the present words; the masks are the device's to check), 0 if more
 // words are needed, -1 if it can never be one. R slots, nblk blocks, PW present words.
 static inline int64_t ck_view_record_words(const uint64_t *words, uint64_t have, uint64_t R, uint64_t nblk, uint64_t PW) {

@@ -1,10 +1,13 @@
-// gx_ckpt_host.hpp — engine checkpoints (include/gx_ckpt.h): gx_ckpt_save, gx_ckpt_params,
-// gx_ckpt_load and the view coder's kernels. Included by gx_engine.hip after the ABI.
+// gx_ckpt_host.hpp — engine checkpoints (include/gx_ckpt.h): gx_ckpt_save, gx_ckpt_save_coded,
+// gx_ckpt_params, gx_ckpt_load and the coders' kernels. Included by gx_engine.hip after the ABI.
 //
-// The view coder works a chunk of views at a time: as many as fit the device staging area at their
-// worst case (8 + 8 R bytes each). One wave owns one (view, block) unit, a block being the 512 slots
-// of GX_DIGEST_SLOTS: lane i of the wave reads slot 64 q + i of the block for q = 0..7, so the ballot
-// of "differs from base" is mask word q as the file holds it, with no LDS and no atomics.
+// The row coder (gx_ckpt.h ROW CODING) serves the views (rows of R words) and the server times (rows
+// of W = 2 H words) through the same kernels: CkRows names the table, and in the kernels "view" and
+// "R" stand for a row and its length. It works a chunk of rows at a time: as many as fit the device
+// staging area at their worst case (8 + 8 R bytes each). One wave owns one (view, block) unit, a
+// block being the 512 slots of GX_DIGEST_SLOTS: lane i of the wave reads slot 64 q + i of the block
+// for q = 0..7, so the ballot of "differs from base" is mask word q as the file holds it, with no
+// LDS and no atomics.
 //   save   k_ck_base     base[r] = max over the views (one stream over the views)
 //          k_ck_count    literals per unit (second stream)
 //          k_ck_vscan    per view, an ordered scan over its blocks: each block's literal offset and
@@ -16,18 +19,50 @@
 //                        the record's shape, every read bounded by the record's end
 //          k_ck_vscan    literal offsets; sum of the popcounts = n_lit, length = what the host walked
 //          k_ck_expand   rows from base and literals, 16-B loads and stores on even R
+//
+// The FIFO coder (gx_ckpt.h FIFO SECTION) keeps each ring's stored window [fifo_head, fifo_stored):
+//   save   k_ck_fcount   n[v] from hs
+//          k_ck_foffsets ordered exclusive scan of n (one block)
+//          k_ck_fpack    a chunk of consecutive hosts, a team per host (a wave; a block when Q >
+//                        CK_FIFO_WAVE_Q): lane i copies job i, i + T, ... of the window with one 16-B
+//                        load and one 16-B store. The window wraps at most once, so a host reads two
+//                        contiguous runs of its ring and writes one run of the staging area.
+//   load   k_ck_foffsets the same scan, of the file's table
+//          k_ck_funpack  every ring slot written once: its job of the window, or zero outside it;
+//                        checks n[v] <= Q, n[v] = the restored window's length and that the jobs lie
+//                        inside the chunk, else the error word (no read past the chunk's jobs
+//                        whatever the table says)
+#include <stdlib.h>
 #include <sys/stat.h>
 
 #include "gx_ckpt_file.hpp"
 
 #define CK_BS GX_DIGEST_SLOTS
-#define CK_MAX_CHUNK_VIEWS 65536u
+#define CK_MAX_CHUNK_VIEWS 65536u  // rows of a chunk at the most, of either row-coded table
 #define CK_ERR_SHAPE 1u
+#define CK_FIFO_WAVE_Q 1024u  // rings up to this size take a wave per host, larger ones a block
+
+// A table the row coder codes: `rows` rows of W words; t0: the first of its three timing classes
+// (CkStage::time_begin); vec: k_ck_expand's 16-B variant (W even, so every row is 16-B aligned).
+struct CkRows {
+  uint64_t *p;
+  uint32_t W, rows;
+  int t0;
+  bool vec;
+};
+struct CkRowStats {
+  uint32_t chunks = 0, raw = 0;
+};
+static uint32_t ck_nblk(uint32_t W) { return (W + CK_BS - 1) / CK_BS; }
+#define CK_T_VIEW 0
+#define CK_T_SRVT 3
+#define CK_T_FIFO 6
+#define CK_T_N 7
 
 struct CkChunk {
   uint64_t *view;        // the chunk's first row
   const uint64_t *base;  // [R]
-  uint32_t R, nblk, PW, nv;
+  uint32_t R, nblk, PW, nv;  // R: the row's length (the views' R, the server times' W)
   uint32_t *cnt, *loff, *prank;  // [nv][nblk] literals of the unit, literals / present blocks before it in the view
   uint64_t *vnl;                 // [nv] n_lit as the record states it
   uint32_t *vnp;                 // [nv] present blocks
@@ -290,6 +325,72 @@ __global__ __launch_bounds__(256) void k_ck_expand(CkChunk c) {
   }
 }
 
+// ------------------------------------------------------------------------------- FIFO coder --
+struct CkFifo {
+  const gx_host_state *hs;  // the chunk's first host
+  gx_job *ring;             // and its ring
+  const uint32_t *n;        // [nv] the chunk's entries of the count table
+  const uint64_t *off;      // [nv + 1] the table's exclusive scan, from the chunk's first host on
+  uint32_t Q, nv;
+  uint64_t jobs;            // the chunk's jobs as the host summed them: what buf holds
+  gx_job *buf;              // the staging area
+};
+
+__global__ __launch_bounds__(256) void k_ck_fcount(const gx_host_state *hs, uint32_t Hl, uint32_t *n) {
+  const uint32_t v = blockIdx.x * 256 + threadIdx.x;
+  if (v < Hl) n[v] = gld(&hs[v].fifo_stored) - gld(&hs[v].fifo_head);
+}
+
+// off = exclusive scan of n, off[Hl] = the jobs of all hosts (one block)
+__global__ __launch_bounds__(256) void k_ck_foffsets(const uint32_t *n, uint32_t Hl, uint64_t *off) {
+  __shared__ uint64_t s_w[4];
+  uint64_t carry = 0;
+  for (uint32_t v0 = 0; v0 < Hl; v0 += 256) {
+    const uint32_t v = v0 + threadIdx.x;
+    uint64_t tot;
+    const uint64_t pre = carry + ck_block_scan(v < Hl ? (uint64_t)n[v] : 0ull, s_w, &tot);
+    if (v < Hl) off[v] = pre;
+    carry += tot;
+  }
+  if (threadIdx.x == 0) off[Hl] = carry;
+}
+
+// Teams of T lanes, one per host. Job i of the window is ring position (head + i) % Q: no read
+// leaves the ring (the count is clamped to Q) and no store leaves the chunk's c.jobs jobs of buf.
+template <int T>
+__global__ __launch_bounds__(256) void k_ck_fpack(CkFifo c) {
+  const uint32_t v = blockIdx.x * (256 / T) + threadIdx.x / T, t = threadIdx.x % T;
+  if (v >= c.nv) return;
+  const uint32_t n = min(c.n[v], c.Q), h0 = gld(&c.hs[v].fifo_head) % c.Q;
+  const uint64_t o = c.off[v] - c.off[0];
+  const gx_job *ring = c.ring + (size_t)v * c.Q;
+  for (uint32_t i = t; i < n && o + i < c.jobs; i += T) {
+    uint32_t p = h0 + i;  // (h0 < Q, i < Q)
+    if (p >= c.Q) p -= c.Q;
+    gst4(&c.buf[o + i], gld4(&ring[p]));
+  }
+}
+
+// The reverse, over every slot of the ring: slot p holds job (p - head) mod Q of the window, or zero.
+// A host whose count fails a check of gx_ckpt.h FIFO SECTION gets an empty ring and sets *err.
+template <int T>
+__global__ __launch_bounds__(256) void k_ck_funpack(CkFifo c, uint32_t *err) {
+  const uint32_t v = blockIdx.x * (256 / T) + threadIdx.x / T, t = threadIdx.x % T;
+  if (v >= c.nv) return;
+  const uint32_t n = c.n[v], head = gld(&c.hs[v].fifo_head), stored = gld(&c.hs[v].fifo_stored);
+  const uint64_t o = c.off[v] - c.off[0];
+  const bool ok = n <= c.Q && n == stored - head && o <= c.jobs && n <= c.jobs - o;
+  if (!ok && t == 0) atomicOr(err, CK_ERR_SHAPE);
+  const uint32_t h0 = head % c.Q, nn = ok ? n : 0u;
+  gx_job *ring = c.ring + (size_t)v * c.Q;
+  for (uint32_t p = t; p < c.Q; p += T) {
+    const uint32_t i = p >= h0 ? p - h0 : p + c.Q - h0;
+    gx_u32x4 j = {0u, 0u, 0u, 0u};
+    if (i < nn) j = gld4(&c.buf[o + i]);  // o + i < o + n <= c.jobs
+    gst4(&ring[p], j);
+  }
+}
+
 // ------------------------------------------------------------------------------------ host --
 // The staging both directions stream through: one area on the device (the coder's chunk) and two
 // pinned halves the file is written from and read into, `half` bytes each (<= GX_CKPT_STAGE_BYTES).
@@ -369,7 +470,7 @@ struct CkStage {
   }
   void time_end() { (void)hipEventRecord(timed.back(), s); }
   // after the stream is idle
-  void time_collect(float *ms /* [3] */) {
+  void time_collect(float *ms /* [CK_T_N] */) {
     for (size_t i = 0; i < timed_cls.size(); i++) {
       float x = 0;
       if (hipEventElapsedTime(&x, timed[2 * i], timed[2 * i + 1]) == hipSuccess) ms[timed_cls[i]] += x;
@@ -378,22 +479,22 @@ struct CkStage {
   }
 };
 
-// views per chunk: what fits the staging half at 8 + 8 R bytes each
-static uint32_t ck_chunk_views(const Dev &d, size_t half) {
-  const uint64_t rec = 8ull * (1 + (uint64_t)d.R);
+// rows of table t per chunk: what fits the staging half at 8 + 8 W bytes each
+static uint32_t ck_chunk_rows(const CkRows &t, size_t half) {
+  const uint64_t rec = 8ull * (1 + (uint64_t)t.W);
   uint64_t n = half / rec;
-  if (n > d.Hl) n = d.Hl;
+  if (n > t.rows) n = t.rows;
   if (n > CK_MAX_CHUNK_VIEWS) n = CK_MAX_CHUNK_VIEWS;
   // the units of a chunk are counted in 32 bits
-  while (n > 1 && n * (uint64_t)d.nblk_ae > 0x7fffffffull) n /= 2;
+  while (n > 1 && n * (uint64_t)ck_nblk(t.W) > 0x7fffffffull) n /= 2;
   return (uint32_t)n;
 }
-// the per-chunk arrays of CkChunk for chunks of cv views
-static int ck_chunk_alloc(DevMem &tmp, const Dev &d, uint32_t cv, CkChunk *c, uint32_t **err, hipStream_t s) {
-  const size_t nu = (size_t)cv * d.nblk_ae;
-  c->R = d.R;
-  c->nblk = d.nblk_ae;
-  c->PW = (d.nblk_ae + 63) / 64;
+// the per-chunk arrays of CkChunk for chunks of cv rows of table t
+static int ck_chunk_alloc(DevMem &tmp, const CkRows &t, uint32_t cv, CkChunk *c, uint32_t **err, hipStream_t s) {
+  const size_t nu = (size_t)cv * ck_nblk(t.W);
+  c->R = t.W;
+  c->nblk = ck_nblk(t.W);
+  c->PW = (c->nblk + 63) / 64;
   GXTRY(tmp.take(c->cnt, sizeof(uint32_t) * nu));
   GXTRY(tmp.take(c->loff, sizeof(uint32_t) * nu));
   GXTRY(tmp.take(c->prank, sizeof(uint32_t) * nu));
@@ -404,47 +505,70 @@ static int ck_chunk_alloc(DevMem &tmp, const Dev &d, uint32_t cv, CkChunk *c, ui
   return tmp.take(*err, sizeof(uint32_t), 0, s);
 }
 
-// The staging half an engine's checkpoint streams through: the largest piece, GX_CKPT_STAGE_BYTES at most.
-static int ck_half_bytes(const gx_engine *e, size_t *half) {
-  const Dev &d = e->d;
-  const uint64_t rec = 8ull * (1 + (uint64_t)d.R);
-  if (rec > GX_CKPT_STAGE_BYTES) return GX_ENOMEM;  // gx_ckpt.h MEMORY
-  uint64_t want = rec * std::min<uint64_t>(d.Hl ? d.Hl : 1, CK_MAX_CHUNK_VIEWS);
-  for (const DevMem::Buf &b : e->mem.bufs)
-    if (b.id && b.id != GX_CK_VIEW) want = std::max<uint64_t>(want, b.bytes);
-  *half = (size_t)std::min<uint64_t>(want, GX_CKPT_STAGE_BYTES);
+// The tables of an engine the row coder may code.
+static CkRows ck_rows_views(const gx_engine *e) { return {e->d.view, e->d.R, e->d.Hl, CK_T_VIEW, vec_of(e)}; }
+// gx_server_times [Hl][H] as words: W = 2 H is even whatever R is
+static CkRows ck_rows_srvt(const gx_engine *e) { return {(uint64_t *)e->d.srvt, 2 * e->d.H, e->d.Hl, CK_T_SRVT, true}; }
+
+// gx_ckpt.h MEMORY: GX_CKPT_STAGE_BYTES, or the smaller value the environment gives at this call.
+static int ck_stage_cap(uint64_t *cap) {
+  *cap = GX_CKPT_STAGE_BYTES;
+  const char *s = getenv("GX_CKPT_STAGE_BYTES");
+  if (!s || !*s) return GX_OK;
+  char *end = nullptr;
+  const unsigned long long v = strtoull(s, &end, 10);
+  if (*end || !v || v % 8) return GX_EINVAL;
+  if (v < *cap) *cap = v;
   return GX_OK;
 }
 
-static int ck_save_views(gx_engine *e, CkStage &st, gx_ckpt_info *info) {
+// The staging half an engine's checkpoint streams through: the largest piece, the cap at most. srvt,
+// fifo: this call codes or decodes that section.
+static int ck_half_bytes(const gx_engine *e, bool srvt, bool fifo, size_t *half) {
   const Dev &d = e->d;
+  uint64_t cap;
+  GXTRY(ck_stage_cap(&cap));
+  const uint64_t rows = std::min<uint64_t>(d.Hl ? d.Hl : 1, CK_MAX_CHUNK_VIEWS);
+  const uint64_t rec = 8ull * (1 + (uint64_t)d.R), rec_t = 8ull * (1 + 2ull * d.H), rec_f = sizeof(gx_job) * (uint64_t)d.Q;
+  // gx_ckpt.h MEMORY: one worst-case record of every coded section fits
+  if (rec > cap || (srvt && rec_t > cap) || (fifo && rec_f > cap)) return GX_ENOMEM;
+  uint64_t want = rec * rows;
+  if (srvt) want = std::max(want, rec_t * rows);
+  for (const DevMem::Buf &b : e->mem.bufs)
+    if (b.id && b.id != GX_CK_VIEW) want = std::max<uint64_t>(want, b.bytes);
+  *half = (size_t)std::min<uint64_t>(want, cap);
+  return GX_OK;
+}
+
+// One row-coded section of table t, to the file.
+static int ck_save_rows(gx_engine *e, CkStage &st, const CkRows &t, CkRowStats *stats) {
   hipStream_t s = e->stream;
   DevMem tmp;  // freed on return; the hipStreamSynchronize below runs first, so no kernel still reads it
-  const uint32_t cv = ck_chunk_views(d, st.half);
-  if (!cv) return d.Hl ? GX_ENOMEM : GX_OK;
+  const uint32_t cv = ck_chunk_rows(t, st.half);
+  if (!cv) return t.rows ? GX_ENOMEM : GX_OK;
   CkChunk c{};
   uint32_t *err;
   unsigned long long *base;
-  GXTRY(tmp.take(base, sizeof(uint64_t) * d.R, 0, s));
-  GXTRY(ck_chunk_alloc(tmp, d, cv, &c, &err, s));
+  GXTRY(tmp.take(base, sizeof(uint64_t) * t.W, 0, s));
+  GXTRY(ck_chunk_alloc(tmp, t, cv, &c, &err, s));
   c.base = (const uint64_t *)base;
   c.buf = (uint64_t *)st.dev;
   int rc = GX_OK;
   auto body = [&]() -> int {
-    st.time_begin(0);
-    const unsigned gx = nblk(d.R, 256);
-    const unsigned vg = std::max(1u, std::min(d.Hl, 4096u / std::min(gx, 4096u)));
-    k_ck_base<<<dim3(gx, vg), 256, 0, s>>>(d.view, d.R, d.Hl, base);
+    st.time_begin(t.t0);
+    const unsigned gx = nblk(t.W, 256);
+    const unsigned vg = std::max(1u, std::min(t.rows, 4096u / std::min(gx, 4096u)));
+    k_ck_base<<<dim3(gx, vg), 256, 0, s>>>(t.p, t.W, t.rows, base);
     st.time_end();
     HIPCHK(hipGetLastError());
-    for (uint64_t o = 0; o < 8ull * d.R; o += st.half)
-      GXTRY(st.push((const uint8_t *)base + o, (size_t)std::min<uint64_t>(st.half, 8ull * d.R - o)));
+    for (uint64_t o = 0; o < 8ull * t.W; o += st.half)
+      GXTRY(st.push((const uint8_t *)base + o, (size_t)std::min<uint64_t>(st.half, 8ull * t.W - o)));
     std::vector<uint64_t> vnl(cv);
-    for (uint32_t v0 = 0; v0 < d.Hl; v0 += cv) {
-      c.nv = std::min(cv, d.Hl - v0);
-      c.view = d.view + (size_t)v0 * d.R;
+    for (uint32_t v0 = 0; v0 < t.rows; v0 += cv) {
+      c.nv = std::min(cv, t.rows - v0);
+      c.view = t.p + (size_t)v0 * t.W;
       const unsigned gu = nblk((size_t)c.nv * c.nblk, 4);
-      st.time_begin(1);
+      st.time_begin(t.t0 + 1);
       k_ck_count<<<gu, 256, 0, s>>>(c);
       k_ck_vscan<true><<<c.nv, 256, 0, s>>>(c, err);
       k_ck_offsets<<<1, 256, 0, s>>>(c);
@@ -455,20 +579,78 @@ static int ck_save_views(gx_engine *e, CkStage &st, gx_ckpt_info *info) {
       HIPCHK(hipMemcpyAsync(vnl.data(), c.vnl, sizeof(uint64_t) * c.nv, hipMemcpyDeviceToHost, s));
       HIPCHK(hipStreamSynchronize(s));
       if (8 * words > st.half) return GX_EIO;  // (cannot happen: a record is at most 8 + 8 R bytes)
-      st.time_begin(2);
+      st.time_begin(t.t0 + 2);
       k_ck_emit<<<gu, 256, 0, s>>>(c);
       st.time_end();
       HIPCHK(hipGetLastError());
       GXTRY(st.push(st.dev, (size_t)(8 * words)));
-      if (info) {
-        info->chunks++;
-        for (uint32_t i = 0; i < c.nv; i++) info->views_raw += vnl[i] == ~0ull;
-      }
+      stats->chunks++;
+      for (uint32_t i = 0; i < c.nv; i++) stats->raw += vnl[i] == ~0ull;
     }
     return st.drain();
   };
   rc = body();
   (void)hipStreamSynchronize(s);  // before tmp goes
+  return rc;
+}
+
+// The device side of a FIFO section: the count table (padded to 8 bytes, the padding zero) and its scan.
+struct CkFifoTab {
+  DevMem mem;
+  uint32_t *n = nullptr;
+  uint64_t *off = nullptr;
+  int init(uint32_t Hl, hipStream_t s) {
+    GXTRY(mem.take(n, (size_t)ck_pad8(4ull * Hl), 0, s));
+    return mem.take(off, sizeof(uint64_t) * ((size_t)Hl + 1));
+  }
+};
+template <class F>
+static void ck_fifo_team(uint32_t Q, F &&f) {
+  if (Q > CK_FIFO_WAVE_Q) f(std::integral_constant<int, 256>{});
+  else f(std::integral_constant<int, 64>{});
+}
+
+// The FIFO section, to the file: the count table, then chunks of consecutive hosts' windows.
+static int ck_save_fifo(gx_engine *e, CkStage &st, uint32_t *chunks, uint64_t *jobs_out) {
+  const Dev &d = e->d;
+  hipStream_t s = e->stream;
+  if (!d.Hl) return GX_OK;
+  CkFifoTab tab;  // freed on return, after the hipStreamSynchronize below
+  GXTRY(tab.init(d.Hl, s));
+  auto body = [&]() -> int {
+    st.time_begin(CK_T_FIFO);
+    k_ck_fcount<<<nblk(d.Hl, 256), 256, 0, s>>>(d.hs, d.Hl, tab.n);
+    k_ck_foffsets<<<1, 256, 0, s>>>(tab.n, d.Hl, tab.off);
+    st.time_end();
+    HIPCHK(hipGetLastError());
+    std::vector<uint32_t> n(d.Hl);
+    HIPCHK(hipMemcpyAsync(n.data(), tab.n, sizeof(uint32_t) * d.Hl, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    for (uint32_t v = 0; v < d.Hl; v++)
+      if (n[v] > d.Q) return GX_EIO;  // (cannot happen: the stored window never exceeds the ring)
+    const uint64_t tb = ck_pad8(4ull * d.Hl);
+    for (uint64_t o = 0; o < tb; o += st.half)
+      GXTRY(st.push((const uint8_t *)tab.n + o, (size_t)std::min<uint64_t>(st.half, tb - o)));
+    for (uint32_t v0 = 0; v0 < d.Hl;) {
+      uint64_t jobs;
+      const uint32_t nv = ck_fifo_chunk_hosts(n.data(), v0, d.Hl, st.half, &jobs);
+      if (!nv) return GX_ENOMEM;  // (cannot happen: ck_half_bytes, n <= Q)
+      if (jobs) {
+        const CkFifo c{d.hs + v0, d.fifo + (size_t)v0 * d.Q, tab.n + v0, tab.off + v0, d.Q, nv, jobs, (gx_job *)st.dev};
+        st.time_begin(CK_T_FIFO);
+        ck_fifo_team(d.Q, [&](auto T) { k_ck_fpack<T()><<<nblk(nv, 256 / T()), 256, 0, s>>>(c); });
+        st.time_end();
+        HIPCHK(hipGetLastError());
+        GXTRY(st.push(st.dev, (size_t)(sizeof(gx_job) * jobs)));
+        ++*chunks;
+        *jobs_out += jobs;
+      }
+      v0 += nv;
+    }
+    return st.drain();
+  };
+  const int rc = body();
+  (void)hipStreamSynchronize(s);  // before tab goes
   return rc;
 }
 
@@ -482,21 +664,32 @@ static void ck_info_section(gx_ckpt_info *info, const CkSection &x) {
   info->raw_bytes += x.raw;
   info->stored_bytes += x.stored;
 }
-static void ck_info_times(gx_ckpt_info *info, CkStage &st) {
-  if (!info) return;
-  float ms[3] = {0, 0, 0};
+static void ck_info_times(gx_ckpt_info *info, gx_ckpt_coded_info *coded, CkStage &st) {
+  if (!info && !coded) return;
+  float ms[CK_T_N] = {0};
   st.time_collect(ms);
-  info->base_ms = ms[0];
-  info->count_ms = ms[1];
-  info->emit_ms = ms[2];
-  info->coder_ms = ms[0] + ms[1] + ms[2];
+  if (info) {
+    info->base_ms = ms[CK_T_VIEW];
+    info->count_ms = ms[CK_T_VIEW + 1];
+    info->emit_ms = ms[CK_T_VIEW + 2];
+    info->coder_ms = info->base_ms + info->count_ms + info->emit_ms;
+  }
+  if (coded) {
+    coded->srvt_base_ms = ms[CK_T_SRVT];
+    coded->srvt_count_ms = ms[CK_T_SRVT + 1];
+    coded->srvt_emit_ms = ms[CK_T_SRVT + 2];
+    coded->srvt_ms = coded->srvt_base_ms + coded->srvt_count_ms + coded->srvt_emit_ms;
+    coded->fifo_ms = ms[CK_T_FIFO];
+  }
 }
 
-static int ck_save(gx_engine *e, const char *path, gx_ckpt_info *info, bool *opened) {
+static int ck_save(gx_engine *e, const char *path, uint32_t code, gx_ckpt_info *info, gx_ckpt_coded_info *coded, bool *opened) {
   Dev &d = e->d;
   HIPCHK(hipStreamSynchronize(e->stream));
+  const bool srvt = (code & GX_CKPT_CODE_SRVT) && e->mem.find(GX_CK_SRVT);
+  const bool fifo = (code & GX_CKPT_CODE_FIFO) && e->mem.find(GX_CK_FIFO);
   size_t half;
-  GXTRY(ck_half_bytes(e, &half));
+  GXTRY(ck_half_bytes(e, srvt, fifo, &half));
   CkStage st;
   GXTRY(st.init(e->stream, half, true, false));
   st.f = fopen(path, "wb");
@@ -514,10 +707,33 @@ static int ck_save(gx_engine *e, const char *path, gx_ckpt_info *info, bool *ope
   if (fwrite(blank.data(), 1, blank.size(), st.f) != blank.size()) return GX_EIO;
   const uint8_t zero[8] = {0};
   for (const DevMem::Buf *b : bufs) {
-    CkSection x{b->id, b->id == GX_CK_VIEW ? GX_CKPT_VIEWS : GX_CKPT_RAW, b->bytes, 0, 0, 0};
+    CkSection x{b->id, GX_CKPT_RAW, b->bytes, 0, 0, 0};
     st.sum = CkSum();
-    if (x.coding == GX_CKPT_VIEWS) {
-      GXTRY(ck_save_views(e, st, info));
+    if (b->id == GX_CK_VIEW) {
+      x.coding = GX_CKPT_VIEWS;
+      CkRowStats rs;
+      GXTRY(ck_save_rows(e, st, ck_rows_views(e), &rs));
+      if (info) {
+        info->chunks = rs.chunks;
+        info->views_raw = rs.raw;
+      }
+    } else if (b->id == GX_CK_SRVT && srvt) {
+      x.coding = GX_CKPT_VIEWS;
+      CkRowStats rs;
+      GXTRY(ck_save_rows(e, st, ck_rows_srvt(e), &rs));
+      if (coded) {
+        coded->srvt_chunks = rs.chunks;
+        coded->srvt_rows_raw = rs.raw;
+      }
+    } else if (b->id == GX_CK_FIFO && fifo) {
+      x.coding = GX_CKPT_FIFO;
+      uint32_t chunks = 0;
+      uint64_t jobs = 0;
+      GXTRY(ck_save_fifo(e, st, &chunks, &jobs));
+      if (coded) {
+        coded->fifo_chunks = chunks;
+        coded->fifo_jobs = jobs;
+      }
     } else {
       for (size_t o = 0; o < b->bytes; o += st.half)
         GXTRY(st.push((const uint8_t *)b->p + o, std::min(st.half, b->bytes - o)));
@@ -537,7 +753,7 @@ static int ck_save(gx_engine *e, const char *path, gx_ckpt_info *info, bool *ope
   st.f = nullptr;
   if (bad) return GX_EIO;
   HIPCHK(hipStreamSynchronize(e->stream));
-  ck_info_times(info, st);
+  ck_info_times(info, coded, st);
   return GX_OK;
 }
 
@@ -589,35 +805,35 @@ static int ck_load_raw(CkStage &st, FILE *f, void *dst, uint64_t bytes) {
   return GX_OK;
 }
 
-static int ck_load_views(gx_engine *e, CkStage &st, FILE *f, const CkSection &x, gx_ckpt_info *info) {
-  const Dev &d = e->d;
+// One row-coded section of the file into table t.
+static int ck_load_rows(gx_engine *e, CkStage &st, FILE *f, const CkSection &x, const CkRows &t, CkRowStats *stats) {
   hipStream_t s = e->stream;
-  if (x.stored % 8 || x.stored < 8ull * d.R) return GX_EIO;
+  if (x.stored % 8 || x.stored < 8ull * t.W) return GX_EIO;
   DevMem tmp;
-  const uint32_t cv = ck_chunk_views(d, st.half);
-  if (!cv) return d.Hl ? GX_ENOMEM : GX_OK;
+  const uint32_t cv = ck_chunk_rows(t, st.half);
+  if (!cv) return t.rows ? GX_ENOMEM : GX_OK;
   CkChunk c{};
   uint32_t *err;
   uint64_t *base;
-  GXTRY(tmp.take(base, sizeof(uint64_t) * d.R));
-  GXTRY(ck_chunk_alloc(tmp, d, cv, &c, &err, s));
+  GXTRY(tmp.take(base, sizeof(uint64_t) * t.W));
+  GXTRY(ck_chunk_alloc(tmp, t, cv, &c, &err, s));
   c.base = base;
   c.buf = (uint64_t *)st.dev;
   auto body = [&]() -> int {
-    GXTRY(ck_load_raw(st, f, base, 8ull * d.R));
+    GXTRY(ck_load_raw(st, f, base, 8ull * t.W));
     GXTRY(ck_half_free(st, 0));
     GXTRY(ck_half_free(st, 1));
-    uint64_t left = x.stored - 8ull * d.R;  // of the section, not read yet
+    uint64_t left = x.stored - 8ull * t.W;  // of the section, not read yet
     size_t have = 0, pos = 0;  // pin[k] holds `have` bytes of the section; the records before `pos` are decoded
     int k = 0;
     uint32_t v0 = 0;
-    while (v0 < d.Hl) {
+    while (v0 < t.rows) {
       // the complete records at the cursor
       const uint64_t *w = (const uint64_t *)(st.pin[k] + pos);
       uint64_t at = 0;
       uint32_t nv = 0;
-      while (nv < cv && v0 + nv < d.Hl) {
-        const int64_t len = ck_view_record_words(w + at, (have - pos) / 8 - at, d.R, c.nblk, c.PW);
+      while (nv < cv && v0 + nv < t.rows) {
+        const int64_t len = ck_view_record_words(w + at, (have - pos) / 8 - at, t.W, c.nblk, c.PW);
         if (len < 0) return GX_EIO;
         if (!len) break;
         st.voff_pin[nv++] = at;
@@ -641,11 +857,11 @@ static int ck_load_views(gx_engine *e, CkStage &st, FILE *f, const CkSection &x,
       }
       st.voff_pin[nv] = at;
       c.nv = nv;
-      c.view = d.view + (size_t)v0 * d.R;
+      c.view = t.p + (size_t)v0 * t.W;
       HIPCHK(hipMemcpyAsync(st.dev, w, (size_t)(8 * at), hipMemcpyHostToDevice, s));
       HIPCHK(hipMemcpyAsync(c.voff, st.voff_pin, sizeof(uint64_t) * (nv + 1), hipMemcpyHostToDevice, s));
       const unsigned gu = nblk((size_t)nv * c.nblk, 4);
-      st.time_begin(1);
+      st.time_begin(t.t0 + 1);
       k_ck_dcount<<<gu, 256, 0, s>>>(c, err);
       k_ck_vscan<false><<<nv, 256, 0, s>>>(c, err);
       st.time_end();
@@ -654,14 +870,12 @@ static int ck_load_views(gx_engine *e, CkStage &st, FILE *f, const CkSection &x,
       HIPCHK(hipMemcpyAsync(&bad, err, sizeof(bad), hipMemcpyDeviceToHost, s));
       HIPCHK(hipStreamSynchronize(s));
       if (bad) return GX_EIO;
-      st.time_begin(2);
-      with_flag(vec_of(e), [&](auto V) { k_ck_expand<V()><<<gu, 256, 0, s>>>(c); });
+      st.time_begin(t.t0 + 2);
+      with_flag(t.vec, [&](auto V) { k_ck_expand<V()><<<gu, 256, 0, s>>>(c); });
       st.time_end();
       HIPCHK(hipGetLastError());
-      if (info) {
-        info->chunks++;
-        for (uint32_t i = 0; i < nv; i++) info->views_raw += w[st.voff_pin[i]] == ~0ull;
-      }
+      stats->chunks++;
+      for (uint32_t i = 0; i < nv; i++) stats->raw += w[st.voff_pin[i]] == ~0ull;
       pos += (size_t)(8 * at);
       v0 += nv;
     }
@@ -672,15 +886,71 @@ static int ck_load_views(gx_engine *e, CkStage &st, FILE *f, const CkSection &x,
   return rc;
 }
 
+// The FIFO section of the file into the rings. The host states are restored already, on the same
+// stream (ck_head_read: their section is in the file, ahead of this one). The host walks the count
+// table (ck_fifo_table_jobs) before a kernel sees it; k_ck_funpack compares it with the host states.
+static int ck_load_fifo(gx_engine *e, CkStage &st, FILE *f, const CkSection &x) {
+  const Dev &d = e->d;
+  hipStream_t s = e->stream;
+  if (!d.Hl) return x.stored ? GX_EIO : GX_OK;
+  const uint64_t tb = ck_pad8(4ull * d.Hl);
+  if (x.stored < tb) return GX_EIO;
+  std::vector<uint32_t> n((size_t)(tb / 4));
+  if (fread(n.data(), 1, (size_t)tb, f) != tb) return GX_EIO;
+  if (ck_fifo_table_jobs(n.data(), tb, d.Hl, d.Q, x.stored) < 0) return GX_EIO;
+  CkFifoTab tab;
+  uint32_t *err;
+  GXTRY(tab.init(d.Hl, s));
+  GXTRY(tab.mem.take(err, sizeof(uint32_t), 0, s));
+  auto body = [&]() -> int {
+    HIPCHK(hipMemcpyAsync(tab.n, n.data(), (size_t)tb, hipMemcpyHostToDevice, s));
+    st.time_begin(CK_T_FIFO);
+    k_ck_foffsets<<<1, 256, 0, s>>>(tab.n, d.Hl, tab.off);
+    st.time_end();
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s));  // n is pageable: the copy has left it
+    for (uint32_t v0 = 0; v0 < d.Hl;) {
+      uint64_t jobs;
+      const uint32_t nv = ck_fifo_chunk_hosts(n.data(), v0, d.Hl, st.half, &jobs);
+      if (!nv) return GX_ENOMEM;  // (cannot happen: ck_half_bytes, n <= Q)
+      const size_t bytes = (size_t)(sizeof(gx_job) * jobs);
+      const int k = st.k;
+      GXTRY(ck_half_free(st, k));
+      if (bytes && fread(st.pin[k], 1, bytes, f) != bytes) return GX_EIO;
+      // (the copy into the one staging area waits, in stream order, for the kernel before it)
+      if (bytes) HIPCHK(hipMemcpyAsync(st.dev, st.pin[k], bytes, hipMemcpyHostToDevice, s));
+      const CkFifo c{d.hs + v0, d.fifo + (size_t)v0 * d.Q, tab.n + v0, tab.off + v0, d.Q, nv, jobs, (gx_job *)st.dev};
+      st.time_begin(CK_T_FIFO);
+      ck_fifo_team(d.Q, [&](auto T) { k_ck_funpack<T()><<<nblk(nv, 256 / T()), 256, 0, s>>>(c, err); });
+      st.time_end();
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipEventRecord(st.ev[k], s));
+      st.busy[k] = true;
+      st.k ^= 1;
+      v0 += nv;
+    }
+    uint32_t bad = 0;
+    HIPCHK(hipMemcpyAsync(&bad, err, sizeof(bad), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return bad ? GX_EIO : GX_OK;
+  };
+  const int rc = body();
+  (void)hipStreamSynchronize(s);  // before tab goes
+  return rc;
+}
+
 static int ck_load_into(gx_engine *e, FILE *f, const CkHeader &h, gx_ckpt_info *info) {
   Dev &d = e->d;
   // each section against the buffer gx_create allocated for these params
+  bool srvt = false, fifo = false;
   for (const CkSection &x : h.sec) {
     const DevMem::Buf *b = e->mem.find(x.id);
     if (b && b->bytes != x.raw) return GX_EINVAL;
+    if (b && x.id == GX_CK_SRVT && x.coding == GX_CKPT_VIEWS) srvt = true;
+    if (b && x.coding == GX_CKPT_FIFO) fifo = true;
   }
   size_t half;
-  GXTRY(ck_half_bytes(e, &half));
+  GXTRY(ck_half_bytes(e, srvt, fifo, &half));
   CkStage st;
   GXTRY(st.init(e->stream, half, true, true));
   GXTRY(ck_verify(f, h, st.pin[0], st.half));
@@ -688,12 +958,22 @@ static int ck_load_into(gx_engine *e, FILE *f, const CkHeader &h, gx_ckpt_info *
     const DevMem::Buf *b = e->mem.find(x.id);
     if (!b) continue;  // gx_ckpt.h FORK: a section the new engine lacks holds its initial state
     if (fseek(f, (long)x.at, SEEK_SET)) return GX_EIO;
-    if (x.coding == GX_CKPT_VIEWS) GXTRY(ck_load_views(e, st, f, x, info));
-    else GXTRY(ck_load_raw(st, f, b->p, x.stored));
+    if (x.coding == GX_CKPT_VIEWS) {  // (ck_head_read: GX_CK_VIEW or GX_CK_SRVT)
+      CkRowStats rs;
+      GXTRY(ck_load_rows(e, st, f, x, x.id == GX_CK_VIEW ? ck_rows_views(e) : ck_rows_srvt(e), &rs));
+      if (info && x.id == GX_CK_VIEW) {
+        info->chunks = rs.chunks;
+        info->views_raw = rs.raw;
+      }
+    } else if (x.coding == GX_CKPT_FIFO) {
+      GXTRY(ck_load_fifo(e, st, f, x));
+    } else {
+      GXTRY(ck_load_raw(st, f, b->p, x.stored));
+    }
     ck_info_section(info, x);
   }
   HIPCHK(hipStreamSynchronize(e->stream));
-  ck_info_times(info, st);
+  ck_info_times(info, nullptr, st);
   d.round = h.round;
   set_round_fields(e);
   quiet_invalidate(e);
@@ -702,13 +982,16 @@ static int ck_load_into(gx_engine *e, FILE *f, const CkHeader &h, gx_ckpt_info *
 
 extern "C" {
 
-int gx_ckpt_save(gx_engine *e, const char *path, gx_ckpt_info *info) {
-  if (!e || !path) return GX_EINVAL;
+int gx_ckpt_save(gx_engine *e, const char *path, gx_ckpt_info *info) { return gx_ckpt_save_coded(e, path, 0, info, nullptr); }
+
+int gx_ckpt_save_coded(gx_engine *e, const char *path, uint32_t code, gx_ckpt_info *info, gx_ckpt_coded_info *coded) {
+  if (!e || !path || (code & ~(GX_CKPT_CODE_SRVT | GX_CKPT_CODE_FIFO))) return GX_EINVAL;
   if (e->round_open || e->side_pending) return GX_EINVAL;  // gx_ckpt.h: only between rounds
   GXTRY(enter(e, ENTRY_READ));
   ck_info_begin(info);
+  if (coded) memset(coded, 0, sizeof(*coded));
   bool opened = false;
-  const int rc = ck_save(e, path, info, &opened);
+  const int rc = ck_save(e, path, code, info, coded, &opened);
   if (rc) {
     (void)hipGetLastError();
     struct stat sb;  // no half-written file stays (a device node or pipe given as the path does)

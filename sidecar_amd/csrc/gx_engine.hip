@@ -1820,7 +1820,7 @@ int gx_round_gossip_end(gx_engine *e, const void *buf, uint64_t bytes, int *ae) 
 // a sharded engine's push-pull chain: gx_ae_bytes .. gx_ae_merge, gx_ae_claim_*, gx_ae_skip_locked
 #include "gx_ae_chain_host.hpp"
 
-// engine checkpoints of include/gx_ckpt.h: gx_ckpt_save, gx_ckpt_params, gx_ckpt_load
+// engine checkpoints of include/gx_ckpt.h: gx_ckpt_save, gx_ckpt_save_coded, gx_ckpt_params, gx_ckpt_load
 #include "gx_ckpt_host.hpp"
 
 // full-state JSON codec: gx_set_names, gx_local_state_json, gx_decode_state_json,

@@ -147,11 +147,11 @@ class ShardRounds:
     def shard_file(dirname, g: int, G: int) -> str:
         return os.path.join(os.fspath(dirname), f"shard_{g:03d}_of_{G:03d}.gxck")
 
-    def save(self, dirname) -> List[dict]:
+    def save(self, dirname, code=0) -> List[dict]:
         """Every held shard's checkpoint into `dirname` (between rounds: run_rounds has returned);
-        each file's gx_ckpt_info."""
+        each file's gx_ckpt_info. code: Engine.ckpt_save's mask of coded sections."""
         os.makedirs(dirname, exist_ok=True)
-        return [e.ckpt_save(self.shard_file(dirname, e.params.shard_id if self.G > 1 else 0, self.G))
+        return [e.ckpt_save(self.shard_file(dirname, e.params.shard_id if self.G > 1 else 0, self.G), code)
                 for e in self.engines]
 
     @classmethod
